@@ -21,11 +21,24 @@ strong-scaling mode (T values over all ranks, e.g. BASELINE configs[4]:
 under torch.distributed.run with N ranks (a child process, started before
 any GPU call); under torchrun, --gpus must equal WORLD_SIZE.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-"roofline" for the dominant kernel (HIP events on the launch stream) and
-"cpu_baseline" (the reference codec compiled from /root/reference by
-oracle/Makefile, timed on this host's cores on a bounded sample; rank 0,
-N=1 only).
+Prints ONE JSON line on rank 0, including "roofline" for the dominant kernel
+(HIP events on the launch stream, recorded in the timed steps themselves).
+
+A plain run does only what `value` needs: set-up, warm-up, the timed steps,
+the `--dump-outputs` files when asked for, the line.  `--full` adds the rest,
+as before: the round-trip check of the decoded values against the inputs
+(`config.roundtrip_ok`; null without it), "cpu_baseline" (the reference codec
+compiled by oracle/Makefile, timed on this host's cores on a bounded sample;
+rank 0, N=1 only) and the `config4` block (configs[4] measured in the same
+job; N > 1 on the default workload, or --config4).
+
+`--dump-outputs DIR` writes what the last timed step left in the caller's
+output arrays as DIR/<name>.npy (float32; value indices float64), rank 0
+under the plain names and rank r > 0 as <name>.rank<r>.npy: the per-value
+lengths and error codes in full up to DUMP_VALUES values, and the n-byte
+slots of a fixed, seeded sample of values (bytes past a value's length
+zeroed: they are not output).  The inputs are synthetic and seeded, so two
+builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -42,6 +55,10 @@ sys.path.insert(0, ROOT)
 import gibson_amd  # noqa: E402
 from gibson_amd.shard import reduce_stats, shard, spread_stats  # noqa: E402
 
+DUMP_SEED = 0x5EED0D07      # the --dump-outputs sample of values
+DUMP_VALUES = 1 << 20       # per-value arrays: at most this many values (4 MB each)
+DUMP_SLOT_BYTES = 12 << 20  # per byte array: float32 bytes of sampled n-byte slots
+DUMP_MAX_BYTES = 64 * 10 ** 6
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 CHUNK_BYTES = 16 << 30  # codec chunk of a batch past this many input bytes
 RED_DEV = "cpu"         # device of the cross-rank reduction tensors (set in main)
@@ -74,9 +91,15 @@ def parse():
     ap.add_argument("--count", type=int, default=0, help="values per GPU (default: workload's)")
     ap.add_argument("--total", type=int, default=0,
                     help="strong scaling: values over all ranks (rank r takes values r, r+N, ...)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the round-trip check "
+                         "(config.roundtrip_ok), the CPU baseline and the configs[4] block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; at most 64 MB, "
+                         "a fixed seeded sample of the values' bytes)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--config4", action="store_true",
-                    help="also measure BASELINE configs[4] (4M x 16 KiB over the ranks) into a config4 "
+                    help="with --full: also measure BASELINE configs[4] (4M x 16 KiB over the ranks) into a config4 "
                          "block; on by default when N > 1 on the default workload")
     ap.add_argument("--no-config4", action="store_true", help="skip the configs[4] block at N > 1")
     ap.add_argument("--config4-total", type=int, default=4 << 20,
@@ -85,6 +108,8 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (default: the cores this process may run on)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     a.workload_given = bool(a.workload)
     return a
 
@@ -252,15 +277,15 @@ def main():
     if a.mode == "decompress":
         return main_decompress(a, world, rank, dev, cfg_idx, kind, seed, n, count)
 
-    rt = run_roundtrip(a, world, rank, dev, kind, seed, n, count)
+    rt = run_roundtrip(a, world, rank, dev, kind, seed, n, count, a.dump_outputs)
     line = roundtrip_line(a, world, rank, rt, cfg_idx, kind, seed, n, count)
     # N > 1 on the default workload: the driver's 1 -> 8 curve stays on
     # configs[2] (weak scaling, the `value` every N reports), and the line also
     # carries configs[4] -- 4 M x 16 KiB split over the ranks, the config the
     # north star's >= 0.9x per-GPU efficiency target is stated on
     #  -- measured in the same job, with its per-GPU
-    # efficiency against the committed N = 1 figure
-    if wants_config4(a, world):
+    # efficiency against the committed N = 1 figure (--full only)
+    if a.full and wants_config4(a, world):
         del rt
         gibson_amd.release()
         torch.cuda.empty_cache()
@@ -316,7 +341,48 @@ def config4_block(world, r4, total, n):
     return blk
 
 
-def run_roundtrip(a, world, rank, dev, kind, seed, n, count):
+def _dump_pick(count, k):
+    """the value indices a dump keeps: all of them up to k values, else a
+    fixed, seeded, sorted sample of k"""
+    import numpy as np
+    if count <= k:
+        return np.arange(count, dtype=np.int64)
+    return np.sort(np.random.RandomState(DUMP_SEED).choice(count, k, replace=False)).astype(np.int64)
+
+
+def _dump_slots(buf, n, idx, valid):
+    """float32 [len(idx), n]: the n-byte slots of values `idx` in `buf`, the
+    bytes at and past a value's `valid` length zeroed (never written)"""
+    t = torch.as_tensor(idx, device=buf.device)
+    col = torch.arange(n, device=buf.device)
+    keep = col[None, :] < valid[t].to(torch.int64)[:, None]
+    return (buf.view(-1, n)[t] * keep.to(torch.uint8)).float().cpu().numpy()
+
+
+def dump_outputs(dirname, rank, n, per_value, slots):
+    """--dump-outputs: `per_value` {name: tensor of one number per value} and
+    `slots` {name: (buffer of n-byte slots, valid length per value)} to
+    dirname/<name>.npy; with each sampled array the value indices kept, as
+    <name>_values.npy"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, t in per_value.items():
+        idx = _dump_pick(t.numel(), DUMP_VALUES)
+        out[name] = t[torch.as_tensor(idx, device=t.device)].float().cpu().numpy()
+        if len(idx) < t.numel():
+            out[name + "_values"] = idx.astype(np.float64)
+    for name, (buf, valid) in slots.items():
+        idx = _dump_pick(valid.numel(), max(1, DUMP_SLOT_BYTES // (4 * n)))
+        out[name] = _dump_slots(buf, n, idx, valid)
+        out[name + "_values"] = idx.astype(np.float64)
+    assert sum(v.nbytes for v in out.values()) <= DUMP_MAX_BYTES
+    sfx = f".rank{rank}" if rank else ""
+    for name, v in out.items():
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), v)
+
+
+def run_roundtrip(a, world, rank, dev, kind, seed, n, count, dump_dir=""):
     """One workload's timed round trips on this rank: value k of this rank is
     global value rank + k*world, generated into HBM; a step compresses every
     value (out_len n-4) and decodes every success.  Returns this rank's
@@ -379,7 +445,7 @@ def run_roundtrip(a, world, rank, dev, kind, seed, n, count):
                 good = verify(c0, m) and good
 
     for w_ in range(a.warmup):
-        step(False, w_ == 0)
+        step(False, a.full and w_ == 0)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -398,10 +464,19 @@ def run_roundtrip(a, world, rank, dev, kind, seed, n, count):
     ok = clen > 0
     n_ok = int(ok.sum())
     c_bytes = int(clen.to(torch.int64).sum())
-    # sanity (outside the timed region): the last chunk of the last step, and
-    # every chunk in the first warm-up step
+    # sanity (--full, outside the timed region): the last chunk of the last
+    # step, and every chunk in the first warm-up step
     c0 = (nch - 1) * chunk
-    good = verify(c0, count - c0) and good
+    if a.full:
+        good = verify(c0, count - c0) and good
+    if dump_dir:
+        # the streams and their lengths of every value; the decoded values,
+        # lengths and error codes of the last chunk (the decode arena is per
+        # chunk); a value that did not compress has no decoded bytes
+        m = count - c0
+        dump_outputs(dump_dir, rank, n, {"clen": clen, "dlen": dlen[:m], "derr": derr[:m]},
+                     {"comp": (comp, clen),
+                      "dec": (dec[:m * n], torch.where(ok[c0:], dlen[:m], torch.zeros_like(dlen[:m])))})
 
     (k_lo, w_lo), (k_hi, w_hi) = spread_stats([t_comp + t_dec, wall], device=RED_DEV)
     (wall, t_comp_max, t_dec_max), (in_bytes_all, n_ok_all, c_bytes_all, bad_ranks) = reduce_stats(
@@ -459,7 +534,7 @@ def roundtrip_line(a, world, rank, rt, cfg_idx, kind, seed, n, count):
             "compressed_fraction": round(rt["n_ok_all"] / (count * world), 4),
             "ratio": round(rt["c_bytes_all"] / max(1.0, rt["n_ok_all"] * n), 4),
             "kernels": gibson_amd.kernel_info(),
-            "roundtrip_ok": rt["bad_ranks"] == 0,
+            "roundtrip_ok": rt["bad_ranks"] == 0 if a.full else None,
             "chunks": rt["nch"],
             "chunk_values": rt["chunk"],
         },
@@ -482,7 +557,7 @@ def roundtrip_line(a, world, rank, rt, cfg_idx, kind, seed, n, count):
             "read_only_frac": round((count * n + c_bytes) / (t_comp + t_dec) / 1e9 / HBM_PEAK_GBPS, 5),
         },
     }
-    if world == 1 and not a.no_cpu:
+    if a.full and world == 1 and not a.no_cpu:
         cores, note = cpu_cores()
         threads = a.cpu_threads or cores
         cnt = a.cpu_count or min(count, max(4 * threads, (4 << 30) // n))
@@ -546,17 +621,23 @@ def main_decompress(a, world, rank, dev, cfg_idx, kind, seed, n, count):
     wall = time.perf_counter() - t0
     t_dec = sum(e0.elapsed_time(e1) for e0, e1 in ev) / a.steps / 1e3
 
-    # sanity (outside the timed region): every compressed value decodes back
+    # sanity (--full, outside the timed region): every compressed value decodes back
     ok = clen > 0
     n_ok = int(ok.sum())
     c_bytes = int(clen.to(torch.int64).sum())
-    good = bool(((dlen == n) | ~ok).all()) and not bool((derr[ok] != 0).any())
-    for c0 in range(0, count, chunk):
-        m = min(chunk, count - c0)
-        gibson_amd.synth_fill(kind, seed, first + c0 * stride, stride, m, n, src)
-        diff = (dec[c0 * n:(c0 + m) * n].view(m, n) != src[:m * n].view(m, n)).any(dim=1)
-        good = good and not bool((diff & ok[c0:c0 + m]).any())
+    good = True
+    if a.full:
+        good = bool(((dlen == n) | ~ok).all()) and not bool((derr[ok] != 0).any())
+        for c0 in range(0, count, chunk):
+            m = min(chunk, count - c0)
+            gibson_amd.synth_fill(kind, seed, first + c0 * stride, stride, m, n, src)
+            diff = (dec[c0 * n:(c0 + m) * n].view(m, n) != src[:m * n].view(m, n)).any(dim=1)
+            good = good and not bool((diff & ok[c0:c0 + m]).any())
     del src
+    if a.dump_outputs:
+        # a value that did not compress was not decoded: no decoded bytes
+        dump_outputs(a.dump_outputs, rank, n, {"dlen": dlen, "derr": derr},
+                     {"dec": (dec, torch.where(ok, dlen, torch.zeros_like(dlen)))})
 
     (k_lo, w_lo), (k_hi, w_hi) = spread_stats([t_dec, wall], device=RED_DEV)
     (wall, t_dec), (n_ok_all, c_bytes_all, bad_ranks) = reduce_stats(
@@ -593,7 +674,7 @@ def main_decompress(a, world, rank, dev, cfg_idx, kind, seed, n, count):
                 "compressed_fraction": round(n_ok_all / (count * world), 4),
                 "ratio": round(c_bytes_all / max(1.0, out_bytes_all), 4),
                 "kernels": gibson_amd.kernel_info(),
-                "roundtrip_ok": bad_ranks == 0,
+                "roundtrip_ok": bad_ranks == 0 if a.full else None,
             },
             "rank_spread": _spread(world, a.steps, k_lo, k_hi, w_lo, w_hi),
             "roofline": {
@@ -609,7 +690,7 @@ def main_decompress(a, world, rank, dev, cfg_idx, kind, seed, n, count):
                 "per_kernel_ms": {"lzf_decompress": round(t_dec * 1e3, 3)},
             },
         }
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             cores, note = cpu_cores()
             threads = a.cpu_threads or cores
             cnt = a.cpu_count or min(count, max(4 * threads, (4 << 30) // n))

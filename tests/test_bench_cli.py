@@ -29,7 +29,7 @@ def test_bench_small_run(args):
     # checked out (the driver's own runs use the full sizes)
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1",
-                        "--warmup", "0", "--no-cpu"] + args,
+                        "--warmup", "0", "--full", "--no-cpu"] + args,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-800:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -106,7 +106,7 @@ def test_bench_default_is_configs2_with_cpu_baseline():
     sys.path.insert(0, ROOT)
     import bench
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1",
-                        "--warmup", "0", "--cpu-count", "64"],
+                        "--warmup", "0", "--full", "--cpu-count", "64"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-800:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -133,7 +133,7 @@ def test_bench_two_ranks_rehearsal(args):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
-                        "--warmup", "0", "--no-cpu"] + args,
+                        "--warmup", "0", "--full", "--no-cpu"] + args,
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-800:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -149,3 +149,62 @@ def test_bench_two_ranks_rehearsal(args):
         assert c4["baseline_config"] == 4 and c4["roundtrip_ok"] is True
         assert c4["total_values"] == 16384 and c4["values_per_gpu_max"] == 8192
         assert c4["per_gpu_efficiency"] is None          # not the committed N = 1 configuration
+
+
+def test_bench_help_lists_full_and_dump_outputs():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-500:]
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_bench_refuses_zero_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_pick_is_fixed_and_bounded():
+    import numpy as np
+    bench, _ = _args([])
+    assert (bench._dump_pick(48, 48) == np.arange(48)).all()
+    a, b = bench._dump_pick(300, 48), bench._dump_pick(300, 48)
+    assert (a == b).all() and len(a) == 48 and (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 300
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    # a plain run (no --full) times --steps steps, skips the checks and the
+    # CPU leg, and with --dump-outputs leaves what its last step computed:
+    # every value's stream length, and a sample of values' streams and decoded
+    # bytes, here checked against the oracle on the generator's values
+    import json
+
+    import numpy as np
+
+    from tests import oracle_lib
+    import bench
+    count, steps = 300, 2
+    _, kind, seed, n, _ = bench.WORKLOADS["text64k"]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                        "--warmup", "1", "--count", str(count), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-800:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "cpu_baseline" not in line and "config4" not in line and line["config"]["roundtrip_ok"] is None
+    d = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert set(d) == {"clen", "dlen", "derr", "comp", "comp_values", "dec", "dec_values"}
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+    assert sum(v.nbytes for v in d.values()) <= 64 * 10 ** 6
+    assert d["clen"].shape == d["dlen"].shape == d["derr"].shape == (count,)
+    rows = d["comp_values"].astype(np.int64)
+    assert 1 < len(rows) < count and (rows == d["dec_values"]).all()
+    assert d["comp"].shape == d["dec"].shape == (len(rows), n)
+    oracle = oracle_lib.Oracle()
+    for k, i in enumerate(rows[:4]):
+        val = oracle_lib.synth(kind, seed, int(i), n)
+        exp = oracle.compress(val, n - 4)
+        assert exp is not None and d["clen"][i] == len(exp) and d["dlen"][i] == n and d["derr"][i] == 0
+        assert bytes(d["comp"][k].astype(np.uint8)) == exp + b"\0" * (n - len(exp))
+        assert bytes(d["dec"][k].astype(np.uint8)) == val

@@ -8,7 +8,8 @@
 # Steps
 #   tests[:EXPR]        the -m gpu suite (pytest -k EXPR)
 #   smoke               __graft_entry__.smoke()
-#   bench[:ARGS]        bench.py line (ARGS comma-separated, e.g. bench:--workload,json4k)
+#   bench[:ARGS]        bench.py line (ARGS comma-separated, e.g. bench:--workload,json4k; bench:--full adds
+#                       the round-trip check, the CPU baseline and the configs[4] block)
 #   benv:LABEL:ENV:ARGS bench.py ARGS under ENV (VAR=x,VAR2=y) -> bench_LABEL.json
 #   prof:LABEL:ARGS     rocprofv3 --kernel-trace --stats of bench.py ARGS -> kernel_stats_LABEL.txt
 #   pmc:LABEL:ARGS      FETCH_SIZE and WRITE_SIZE passes of bench.py ARGS (one counter per run)
@@ -143,7 +144,7 @@ for st in "$@"; do
       python3 tools/trace_timeline.py $O/trace_$lab run > $O/timeline_$lab.txt || exit 1
       wc -l $O/timeline_$lab.txt ;;
     gpus2)
-      LZF_BENCH_BACKEND=gloo LZF_BENCH_SHARE_GPU=1 timeout -k 10 600 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu > $O/gpus2.json 2> $O/gpus2.err || exit 1
+      LZF_BENCH_BACKEND=gloo LZF_BENCH_SHARE_GPU=1 timeout -k 10 600 python bench.py --gpus 2 --steps 2 --warmup 1 --full --no-cpu > $O/gpus2.json 2> $O/gpus2.err || exit 1
       tail -1 $O/gpus2.json | cut -c1-400 ;;
     calib)
       for c in FETCH_SIZE WRITE_SIZE; do
