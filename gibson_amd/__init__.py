@@ -38,4 +38,16 @@ from .lzf import (  # noqa: F401
     host_split_policy,
     parse_device_list,
     kv_frame,
+    NCLASS,
+    KIND_COMPRESS,
+    KIND_DECOMPRESS,
+    size_class,
+    size_partition,
+    host_size_partition,
+    mixed_work,
+    compress_mixed,
+    decompress_mixed,
+    mixed_last_plan,
+    host_compress_mixed,
+    host_decompress_mixed,
 )

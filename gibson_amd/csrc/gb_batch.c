@@ -32,6 +32,30 @@ static uint32_t gb_needcompr(uint32_t vlen)
     return c < most ? c : most;
 }
 
+/* LZF_GPU_MIXED=1 (read per call): the codec batches go through the
+ * size-class calls (lzf_host_*_mixed), for requests whose value sizes spread
+ * widely; the decisions, streams, stats and frames are the same either way */
+static int gb_mixed(void)
+{
+    const char *e = getenv("LZF_GPU_MIXED");
+    return e && e[0] == '1' && !e[1];
+}
+
+static int gb_compress(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                       const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, uint32_t count)
+{
+    return gb_mixed() ? lzf_host_compress_mixed(in, in_off, in_len, out, out_off, out_cap, out_len, count)
+                      : lzf_host_compress_batch(in, in_off, in_len, out, out_off, out_cap, out_len, count);
+}
+
+static int gb_decompress(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                         const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *err,
+                         uint32_t count)
+{
+    return gb_mixed() ? lzf_host_decompress_mixed(in, in_off, in_len, out, out_off, out_cap, out_len, err, count)
+                      : lzf_host_decompress_batch(in, in_off, in_len, out, out_off, out_cap, out_len, err, count);
+}
+
 int gb_set_batch(const uint8_t *v, const uint64_t *v_off, const uint32_t *v_len, uint32_t n,
                  uint32_t compression, uint8_t *out, const uint64_t *out_off, gb_stored *st,
                  gb_stats *stats)
@@ -66,7 +90,7 @@ int gb_set_batch(const uint8_t *v, const uint64_t *v_off, const uint32_t *v_len,
             cap[k] = gb_needcompr(v_len[i]);
             k++;
         }
-        rc = lzf_host_compress_batch(v, ioff, len, out, ooff, cap, res, m);
+        rc = gb_compress(v, ioff, len, out, ooff, cap, res, m);
         if (rc) goto done;
     }
     /* the stores, and the running mean, in request order */
@@ -223,7 +247,7 @@ long gb_mget_payload(const uint8_t *keys, const uint64_t *key_off, const uint32_
         for (uint32_t k = 0; k < m; k++) dl[k] = 0;
         /* an item of size 0 (does not decode) keeps cap 0: it fails again
          * in the batch, and the frame below stops there as the reference does */
-        int rc = lzf_host_decompress_batch(vals, ioff, len, dec, ooff, cap, dl, er, m);
+        int rc = gb_decompress(vals, ioff, len, dec, ooff, cap, dl, er, m);
         if (rc) {
             ret = rc;
             goto done;
@@ -261,7 +285,7 @@ long gb_mget_payload(const uint8_t *keys, const uint64_t *key_off, const uint32_
                 } else {
                     dec = b;
                     /* items that do not decode at all keep size 0 (us == 0) */
-                    rc2 = lzf_host_decompress_batch(vals, uo, ul, dec, so, us, sl, se, ns);
+                    rc2 = gb_decompress(vals, uo, ul, dec, so, us, sl, se, ns);
                     if (rc2 == LZF_GPU_OK) {
                         for (uint32_t j = 0; j < ns; j++) {
                             if (!us[j] || !sl[j]) continue;

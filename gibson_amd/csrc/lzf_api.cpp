@@ -198,6 +198,15 @@ void scratch_free(Scratch &S)
 enum ScratchUser { SU_LANE = 0, SU_TABLE = 1, SU_WTAB = 2 };
 /* chunks of this thread's last scratch-bound compress launch (kernel_info) */
 thread_local uint32_t g_last_chunks = 0;
+/* the route of this thread's last launch_compress (lzf_gpu_mixed_last_plan) */
+enum Route { ROUTE_NONE = 0, ROUTE_LANE = 1, ROUTE_TABLE = 2, ROUTE_WINDOW = 3, ROUTE_DIAG = 4 };
+thread_local int g_last_route = ROUTE_NONE;
+
+hipError_t window_compress(const LzfBatch &b, hipStream_t s)
+{
+    g_last_route = ROUTE_WINDOW;
+    return lzf_launch_compress(b, s);
+}
 
 /* own: a caller's private scratch (the host pipelines' slots, so their
  * chunks' compress launches can run side by side), else the device's */
@@ -205,6 +214,7 @@ hipError_t lane_compress(const LzfBatch &b, hipStream_t s, ScratchUser who, Scra
                          const LzfParts *parts = nullptr)
 {
     const bool table = who == SU_TABLE;
+    g_last_route = table ? ROUTE_TABLE : who == SU_LANE ? ROUTE_LANE : ROUTE_DIAG;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -314,24 +324,24 @@ hipError_t launch_compress(const LzfBatch &b, hipStream_t s, Scratch *own = null
             if (e != hipSuccess) return e;
         }
     if (!routed_default) parts = nullptr;
-    if (g != GEN_WINDOW && g != GEN_SERIAL && !lds_order_ok()) return lzf_launch_compress(b, s);
+    if (g != GEN_WINDOW && g != GEN_SERIAL && !lds_order_ok()) return window_compress(b, s);
     switch (g) {
 #ifdef LZF_DIAG
-    case GEN_SERIAL: return lzf_launch_compress_serial(b, s);
+    case GEN_SERIAL: g_last_route = ROUTE_DIAG; return lzf_launch_compress_serial(b, s);
 #endif
-    case GEN_WINDOW: return lzf_launch_compress(b, s);
+    case GEN_WINDOW: return window_compress(b, s);
     case GEN_LANE:
         return (lzf_lane_compress_supported(b.max_len) && b.count >= lane_min_count(b.max_len))
                    ? lane_compress(b, s, SU_LANE)
-                   : lzf_launch_compress(b, s);
+                   : window_compress(b, s);
 #ifdef LZF_DIAG
     case GEN_WTAB:
-        return lzf_wtab_compress_supported(b.max_len) ? lane_compress(b, s, SU_WTAB) : lzf_launch_compress(b, s);
+        return lzf_wtab_compress_supported(b.max_len) ? lane_compress(b, s, SU_WTAB) : window_compress(b, s);
 #endif
     case GEN_TABLE_ONLY:
         return (lzf_table_compress_supported(b.max_len) && b.count >= lane_min_count(b.max_len))
                    ? lane_compress(b, s, SU_TABLE)
-                   : lzf_launch_compress(b, s);
+                   : window_compress(b, s);
     default:
         /* batches with values past 64 KiB, and small batches, go to the window
          * generation: the parse runs one value per lane, so its time has a
@@ -345,7 +355,7 @@ hipError_t launch_compress(const LzfBatch &b, hipStream_t s, Scratch *own = null
                 const hipError_t e = hipStreamWaitEvent(s, parts->ev[p], 0);
                 if (e != hipSuccess) return e;
             }
-            return lzf_launch_compress(b, s);
+            return window_compress(b, s);
         }
         /* the lane generation where its kernel 1 takes the batch (a
          * diagnostic LZF_GPU_CAND=small stops at 4 KiB), else the table one --
@@ -413,6 +423,188 @@ int code_of(hipError_t e)
     return LZF_GPU_ELAUNCH;
 }
 
+/* ---- mixed-size batches: one class batch per size class -------------------- */
+
+constexpr uint32_t MIXED_NC = LZF_GPU_NCLASS + 1;
+
+/* whether launch_compress sends this batch to window64 -- its conditions,
+ * read-only.  It only chooses the stream of a class batch (window64 holds no
+ * scratch, so it may run beside the others); were it ever wrong, the scratch's
+ * own event still orders its users across streams. */
+bool compress_goes_window(const LzfBatch &b)
+{
+    const KernelGen g = kernel_gen();
+    if (g == GEN_SERIAL) return false;
+    if (g == GEN_WINDOW || !lds_order_ok()) return true;
+    switch (g) {
+    case GEN_LANE: return !(lzf_lane_compress_supported(b.max_len) && b.count >= lane_min_count(b.max_len));
+#ifdef LZF_DIAG
+    case GEN_WTAB: return !lzf_wtab_compress_supported(b.max_len);
+#endif
+    case GEN_TABLE_ONLY: return !(lzf_table_compress_supported(b.max_len) && b.count >= lane_min_count(b.max_len));
+    default: return b.count < lane_min_count(b.max_len) || !lzf_table_compress_supported(b.max_len);
+    }
+}
+
+/* the decoder lzf_launch_decompress picks for a bound (lzf_decompress.hip:
+ * tokpar64 up to 4 KiB, tokpar64-far up to CD_FAR_MAX = 16 KiB, the pipe past) */
+int decompress_route(uint32_t max_len)
+{
+#ifdef LZF_DIAG
+    if (kernel_gen() == GEN_SERIAL || lane_decoder()) return ROUTE_DIAG;
+#endif
+    return max_len <= 4096u ? 1 : max_len <= 16384u ? 2 : 3;
+}
+
+/* per device: the side stream of the window64 classes with its fork / join
+ * events, and the pinned landing place of the 48-byte plan.  The mutex is
+ * held while a mixed call enqueues (its one wait included), so concurrent
+ * mixed calls on one device take turns. */
+struct Side {
+    std::mutex mu;
+    hipStream_t st = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr, got = nullptr;
+    uint32_t *pin = nullptr;
+};
+Side g_side[64];
+
+void side_free(Side &S)
+{
+    if (S.st) {
+        (void)hipStreamSynchronize(S.st);
+        (void)hipStreamDestroy(S.st);
+    }
+    if (S.fork) (void)hipEventDestroy(S.fork);
+    if (S.join) (void)hipEventDestroy(S.join);
+    if (S.got) (void)hipEventDestroy(S.got);
+    if (S.pin) (void)hipHostFree(S.pin);
+    S.st = nullptr;
+    S.fork = S.join = S.got = nullptr;
+    S.pin = nullptr;
+}
+
+/* this thread's last mixed device call (lzf_gpu_mixed_last_plan) */
+thread_local uint32_t g_plan_count[MIXED_NC], g_plan_max[MIXED_NC];
+thread_local int g_plan_route[MIXED_NC];
+thread_local uint32_t g_last_mixed = 0;
+
+size_t mixed_work_bytes(uint32_t count)
+{
+    /* perm, four descriptor copies, out_len and err copies; the plan; the
+     * partition's tables; room to align the caller's pointer */
+    return (size_t)count * (2u * sizeof(uint64_t) + 5u * sizeof(uint32_t)) + 64u + lzf_partition_work_bytes(count) +
+           16u;
+}
+
+int mixed_call(int kind, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+               const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *err, uint32_t count,
+               uint32_t bound, void *work, hipStream_t s)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LZF_GPU_ENODEV;
+    uint8_t *w = (uint8_t *)(((uintptr_t)work + 15u) & ~(uintptr_t)15u);
+    uint64_t *c_in_off = (uint64_t *)w;
+    uint64_t *c_out_off = c_in_off + count;
+    uint32_t *perm = (uint32_t *)(c_out_off + count);
+    uint32_t *c_in_len = perm + count, *c_out_cap = c_in_len + count, *c_out_len = c_out_cap + count;
+    int32_t *c_err = (int32_t *)(c_out_len + count);
+    uint32_t *plan = (uint32_t *)(c_err + count);           /* class_count, class_max */
+    void *pwork = plan + 16;
+    const bool comp = kind == LZF_GPU_KIND_COMPRESS;
+
+    Side &S = g_side[dev];
+    std::lock_guard<std::mutex> lk(S.mu);
+    hipError_t e;
+    if (!S.pin && (e = hipHostMalloc((void **)&S.pin, 2u * MIXED_NC * sizeof(uint32_t), hipHostMallocDefault)) !=
+                      hipSuccess) {
+        S.pin = nullptr;
+        return code_of(e);
+    }
+    if (!S.got && (e = hipEventCreateWithFlags(&S.got, hipEventDisableTiming)) != hipSuccess) return code_of(e);
+
+    /* partition by the length that picks the plan, compact the descriptors,
+     * and fetch the plan: the call's one wait */
+    if ((e = lzf_launch_size_partition(comp ? in_len : out_cap, count, bound, kind, perm, plan, plan + MIXED_NC,
+                                       pwork, s)) != hipSuccess ||
+        (e = lzf_launch_mixed_gather(perm, count, in_off, in_len, out_off, out_cap, c_in_off, c_in_len, c_out_off,
+                                     c_out_cap, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(S.pin, plan, 2u * MIXED_NC * sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipEventRecord(S.got, s)) != hipSuccess || (e = hipEventSynchronize(S.got)) != hipSuccess)
+        return code_of(e);
+    uint32_t start[MIXED_NC], at = 0;
+    for (uint32_t c = 0; c < MIXED_NC; c++) {
+        g_plan_count[c] = S.pin[c];
+        g_plan_max[c] = S.pin[MIXED_NC + c];
+        g_plan_route[c] = ROUTE_NONE;
+        start[c] = at;
+        at += g_plan_count[c];
+    }
+    if (at != count) return LZF_GPU_ELAUNCH;               /* the partition did not account for every value */
+
+    /* the class batches, largest class first; the window64 ones (compress)
+     * aside, unless nothing else would run on the caller's stream */
+    LzfBatch cb[LZF_GPU_NCLASS];
+    int cls_of[LZF_GPU_NCLASS], main_i[LZF_GPU_NCLASS], side_i[LZF_GPU_NCLASS];
+    uint32_t nb = 0, nmain = 0, nside = 0;
+    for (int c = LZF_GPU_NCLASS - 1; c >= 0; c--) {
+        if (!g_plan_count[c]) continue;
+        const uint32_t o = start[c];
+        cb[nb] = LzfBatch{in,           c_in_off + o,  c_in_len + o,
+                          out,          c_out_off + o, c_out_cap + o,
+                          c_out_len + o, err ? c_err + o : nullptr,
+                          g_plan_count[c], g_plan_max[c] ? g_plan_max[c] : 1u};
+        cls_of[nb] = c;
+        if (comp && g_plan_max[c] && compress_goes_window(cb[nb]))
+            side_i[nside++] = (int)nb;
+        else
+            main_i[nmain++] = (int)nb;
+        nb++;
+    }
+    if (!nmain && nside) {
+        main_i[nmain++] = side_i[0];
+        for (uint32_t k = 1; k < nside; k++) side_i[k - 1] = side_i[k];
+        nside--;
+    }
+    g_last_mixed = nb;
+
+    auto run = [&](int k, hipStream_t st) -> hipError_t {
+        const LzfBatch &b = cb[k];
+        const int c = cls_of[k];
+        if (!comp) {
+            g_plan_route[c] = decompress_route(b.max_len);
+            return launch_decompress(b, st);
+        }
+        if (!g_plan_max[c])              /* a class of empty values: out_len 0 each, as max_in_len 0 does */
+            return hipMemsetAsync(b.out_len, 0, (size_t)b.count * sizeof(uint32_t), st);
+        const hipError_t r = launch_compress(b, st);
+        g_plan_route[c] = g_last_route;
+        return r;
+    };
+
+    hipError_t first = hipSuccess;
+    bool forked = false;
+    if (nside) {
+        if (!S.st) e = hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking);
+        else e = hipSuccess;
+        if (e == hipSuccess && !S.fork) e = hipEventCreateWithFlags(&S.fork, hipEventDisableTiming);
+        if (e == hipSuccess && !S.join) e = hipEventCreateWithFlags(&S.join, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(S.fork, s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(S.st, S.fork, 0);
+        if (e != hipSuccess) return code_of(e);
+        forked = true;
+        for (uint32_t k = 0; k < nside && first == hipSuccess; k++) first = run(side_i[k], S.st);
+    }
+    for (uint32_t k = 0; k < nmain && first == hipSuccess; k++) first = run(main_i[k], s);
+    if (forked) {                        /* joined even after a failure: the side work must not outlive the call's order */
+        e = hipEventRecord(S.join, S.st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, S.join, 0);
+        if (first == hipSuccess) first = e;
+    }
+    if (first != hipSuccess) return code_of(first);
+    e = lzf_launch_mixed_scatter(perm, count, plan, c_out_len, err ? c_err : nullptr, out_len, err, s);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
 }  // namespace
 
 /* the routed launches and the scratch, for the host-memory paths (lzf_host.cpp) */
@@ -456,9 +648,55 @@ void lzf_scratch_release_all(void)
         std::lock_guard<std::mutex> lk(S.mu);
         scratch_free(S);
     }
+    /* the mixed calls' side stream, events and pinned plan */
+    for (Side &S : g_side) {
+        std::lock_guard<std::mutex> lk(S.mu);
+        side_free(S);
+    }
 }
 
 extern "C" {
+
+uint64_t lzf_gpu_mixed_work_size(uint32_t count)
+{
+    return mixed_work_bytes(count);
+}
+
+int lzf_gpu_compress_mixed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                           uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                           uint32_t *out_len, uint32_t count, uint32_t max_in_len, void *work, void *stream)
+{
+    if (!count || !in || !in_off || !in_len || !out || !out_off || !out_cap || !out_len || !work)
+        return LZF_GPU_EARG;
+    if (max_in_len > LZF_GPU_MAX_VALUE) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    return mixed_call(LZF_GPU_KIND_COMPRESS, in, in_off, in_len, out, out_off, out_cap, out_len, nullptr, count,
+                      max_in_len, work, (hipStream_t)stream);
+}
+
+int lzf_gpu_decompress_mixed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                             uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                             uint32_t *out_len, int32_t *err, uint32_t count,
+                             uint32_t max_out_cap, void *work, void *stream)
+{
+    if (!count || !in || !in_off || !in_len || !out || !out_off || !out_cap || !out_len || !err || !work)
+        return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    return mixed_call(LZF_GPU_KIND_DECOMPRESS, in, in_off, in_len, out, out_off, out_cap, out_len, err, count,
+                      max_out_cap, work, (hipStream_t)stream);
+}
+
+int lzf_gpu_mixed_last_plan(uint32_t *class_count, uint32_t *class_max, int *route, int max)
+{
+    for (int c = 0; c < max && c < (int)MIXED_NC; c++) {
+        if (class_count) class_count[c] = g_plan_count[c];
+        if (class_max) class_max[c] = g_plan_max[c];
+        if (route) route[c] = g_plan_route[c];
+    }
+    return (int)g_last_mixed;
+}
 
 int lzf_gpu_compress_batch(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
                            uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
@@ -610,6 +848,8 @@ const char *lzf_gpu_kernel_info(void)
         s += std::string(" lds_order=") + (st == 1 ? "held" : st == -1 ? "violated(compress->window64)"
                                            : st == -2 ? "probe-failed(retried)" : "unchecked");
         if (g_last_chunks) s += " scratch_chunks=" + std::to_string(g_last_chunks);
+        /* class batches of the thread's last mixed call */
+        if (g_last_mixed) s += " mixed=" + std::to_string(g_last_mixed);
     }
     return s.c_str();
 }

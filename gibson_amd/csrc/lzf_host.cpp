@@ -1289,6 +1289,64 @@ int lzf_host_decompress_batch(const uint8_t *in, const uint64_t *in_off, const u
     return host_batch_call(HostArgs{false, in, in_off, in_len, out, out_off, out_cap, out_len, err}, count);
 }
 
+/* The host-memory batches by size class: the lengths are here, so the
+ * partition is the host twin's; every non-empty class is one uniform host
+ * call over class-contiguous copies of the descriptors (the order inside a
+ * class is the request's, so the registered path keeps its DMA adjacency),
+ * and the results go back through the permutation. */
+static int host_mixed_call(bool comp, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                           const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *err,
+                           uint32_t count)
+{
+    if (!count || !in || !in_off || !in_len || !out || !out_off || !out_cap || !out_len || (!comp && !err))
+        return LZF_GPU_EARG;
+    uint32_t cc[LZF_GPU_NCLASS + 1], cm[LZF_GPU_NCLASS + 1];
+    try {
+        std::vector<uint32_t> perm(count), ilen(count), ocap(count), olen(count, 0u);
+        std::vector<uint64_t> ioff(count), ooff(count);
+        std::vector<int32_t> er(comp ? 0u : count, 0);
+        int rc = lzf_host_size_partition(comp ? in_len : out_cap, count, 0xFFFFFFFFu,
+                                         comp ? LZF_GPU_KIND_COMPRESS : LZF_GPU_KIND_DECOMPRESS, perm.data(), cc, cm);
+        if (rc) return rc;
+        for (uint32_t k = 0; k < count; k++) {
+            const uint32_t i = perm[k];
+            ioff[k] = in_off[i];
+            ilen[k] = in_len[i];
+            ooff[k] = out_off[i];
+            ocap[k] = out_cap[i];
+        }
+        uint32_t o = count;
+        for (int c = LZF_GPU_NCLASS - 1; c >= 0; c--) {      /* largest class first */
+            if (!cc[c]) continue;
+            o -= cc[c];
+            rc = comp ? lzf_host_compress_batch(in, &ioff[o], &ilen[o], out, &ooff[o], &ocap[o], &olen[o], cc[c])
+                      : lzf_host_decompress_batch(in, &ioff[o], &ilen[o], out, &ooff[o], &ocap[o], &olen[o], &er[o],
+                                                  cc[c]);
+            if (rc) return rc;
+        }
+        for (uint32_t k = 0; k < count; k++) {
+            out_len[perm[k]] = olen[k];
+            if (!comp) err[perm[k]] = er[k];
+        }
+    } catch (const std::bad_alloc &) {
+        return LZF_GPU_ENOMEM;
+    }
+    return LZF_GPU_OK;
+}
+
+int lzf_host_compress_mixed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                            const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, uint32_t count)
+{
+    return host_mixed_call(true, in, in_off, in_len, out, out_off, out_cap, out_len, nullptr, count);
+}
+
+int lzf_host_decompress_mixed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                              const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *err,
+                              uint32_t count)
+{
+    return host_mixed_call(false, in, in_off, in_len, out, out_off, out_cap, out_len, err, count);
+}
+
 int lzf_host_decoded_size_batch(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
                                 uint32_t *out_size, int32_t *err, uint32_t count, uint32_t out_limit)
 {

@@ -120,6 +120,21 @@ hipError_t lzf_launch_move(const uint8_t *src, const uint64_t *src_off, uint8_t 
  * bytes past a decoded value that a DMA of abutting slots would carry) */
 hipError_t lzf_launch_clear_tail(uint8_t *dst, const uint64_t *dst_off, const uint32_t *len, const uint32_t *cap,
                                  uint32_t count, hipStream_t s);
+/* size classes of a mixed-size batch (lzf_mixed.hip): the stable partition of
+ * `count` lengths into perm / class_count / class_max (work:
+ * lzf_partition_work_bytes, 4-byte aligned), the four descriptor arrays
+ * gathered through perm, and the results scattered back (the refused values
+ * get out_len 0 and err EINVAL; err / c_err NULL for compress) */
+size_t lzf_partition_work_bytes(uint32_t count);
+hipError_t lzf_launch_size_partition(const uint32_t *len, uint32_t count, uint32_t bound, int kind, uint32_t *perm,
+                                     uint32_t *class_count, uint32_t *class_max, void *work, hipStream_t s);
+hipError_t lzf_launch_mixed_gather(const uint32_t *perm, uint32_t count, const uint64_t *in_off,
+                                   const uint32_t *in_len, const uint64_t *out_off, const uint32_t *out_cap,
+                                   uint64_t *c_in_off, uint32_t *c_in_len, uint64_t *c_out_off, uint32_t *c_out_cap,
+                                   hipStream_t s);
+hipError_t lzf_launch_mixed_scatter(const uint32_t *perm, uint32_t count, const uint32_t *class_count,
+                                    const uint32_t *c_out_len, const int32_t *c_err, uint32_t *out_len, int32_t *err,
+                                    hipStream_t s);
 /* lzf_api.cpp, for the host-memory paths of lzf_host.cpp: the routed
  * launches, the routing's batch threshold, the device check, the scratch */
 hipError_t lzf_route_compress(const LzfBatch &b, hipStream_t s);

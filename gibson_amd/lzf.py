@@ -39,7 +39,21 @@ EXPORTS = (
     "lzf_host_split_block",
     "lzf_host_split_policy",
     "lzf_gpu_parse_device_list",
+    "lzf_gpu_size_class",
+    "lzf_gpu_size_partition_work_size",
+    "lzf_gpu_size_partition",
+    "lzf_host_size_partition",
+    "lzf_gpu_mixed_work_size",
+    "lzf_gpu_compress_mixed",
+    "lzf_gpu_decompress_mixed",
+    "lzf_gpu_mixed_last_plan",
+    "lzf_host_compress_mixed",
+    "lzf_host_decompress_mixed",
 )
+
+# size classes of the mixed calls (include/lzf_gpu.h)
+NCLASS = 5
+KIND_COMPRESS, KIND_DECOMPRESS = 0, 1
 
 # item encodings (src/net.h:274-278) and the MGET reply code (src/query.h:71)
 ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
@@ -143,9 +157,38 @@ def _load(path):
     L.lzf_host_split_policy.argtypes = []
     L.lzf_gpu_parse_device_list.restype = ctypes.c_int
     L.lzf_gpu_parse_device_list.argtypes = [ctypes.c_char_p, ctypes.c_int, vp, ctypes.c_int]
+    if hasattr(L, "lzf_gpu_compress_mixed"):
+        _bind_mixed(L)
     del i32
     _LOADED[path] = L
     return L
+
+
+def _bind_mixed(L):
+    """The mixed-size calls.  A build from before they existed, given by
+    LZF_HIP_LIB for an A/B of the uniform calls, has none of them: the mixed
+    helpers below then raise AttributeError, they do not fall back."""
+    u32, u64, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
+    L.lzf_gpu_size_class.restype = ctypes.c_int
+    L.lzf_gpu_size_class.argtypes = [u32, ctypes.c_int]
+    L.lzf_gpu_size_partition_work_size.restype = u64
+    L.lzf_gpu_size_partition_work_size.argtypes = [u32]
+    L.lzf_gpu_size_partition.restype = ctypes.c_int
+    L.lzf_gpu_size_partition.argtypes = [vp, u32, u32, ctypes.c_int, vp, vp, vp, vp, vp]
+    L.lzf_host_size_partition.restype = ctypes.c_int
+    L.lzf_host_size_partition.argtypes = [vp, u32, u32, ctypes.c_int, vp, vp, vp]
+    L.lzf_gpu_mixed_work_size.restype = u64
+    L.lzf_gpu_mixed_work_size.argtypes = [u32]
+    L.lzf_gpu_compress_mixed.restype = ctypes.c_int
+    L.lzf_gpu_compress_mixed.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]
+    L.lzf_gpu_decompress_mixed.restype = ctypes.c_int
+    L.lzf_gpu_decompress_mixed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]
+    L.lzf_gpu_mixed_last_plan.restype = ctypes.c_int
+    L.lzf_gpu_mixed_last_plan.argtypes = [vp, vp, vp, ctypes.c_int]
+    L.lzf_host_compress_mixed.restype = ctypes.c_int
+    L.lzf_host_compress_mixed.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32]
+    L.lzf_host_decompress_mixed.restype = ctypes.c_int
+    L.lzf_host_decompress_mixed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32]
 
 
 def selfcheck():
@@ -259,6 +302,103 @@ def host_decompress_batch(inp, in_off, in_len, out, out_off, out_cap, out_len, e
                                          _np_ptr(out), _np_ptr(out_off), _np_ptr(out_cap),
                                          _np_ptr(out_len), _np_ptr(err), len(in_len))
     _check(rc, "lzf_host_decompress_batch")
+
+
+# ---- mixed-size batches: one class batch per size class --------------------
+
+def size_class(n, kind):
+    """lzf_gpu_size_class(): the class of a length (KIND_COMPRESS: in_len,
+    KIND_DECOMPRESS: out_cap)."""
+    c = int(lib().lzf_gpu_size_class(int(n), int(kind)))
+    if c < 0:
+        raise ValueError(f"lzf_gpu_size_class: bad kind {kind}")
+    return c
+
+
+def size_partition(lens, bound, kind, stream=None):
+    """Device partition of an int32 CUDA tensor of lengths (read as u32):
+    returns (perm, class_count, class_max) as CUDA int32 tensors, the last two
+    of NCLASS + 1 entries (the last: values past ``bound``)."""
+    import torch
+    n = lens.numel()
+    perm = torch.empty(n, dtype=torch.int32, device=lens.device)
+    cc = torch.empty(NCLASS + 1, dtype=torch.int32, device=lens.device)
+    cm = torch.empty(NCLASS + 1, dtype=torch.int32, device=lens.device)
+    work = torch.empty(int(lib().lzf_gpu_size_partition_work_size(n)), dtype=torch.uint8, device=lens.device)
+    _check(lib().lzf_gpu_size_partition(_ptr(lens), n, int(bound), int(kind), _ptr(perm), _ptr(cc), _ptr(cm),
+                                        _ptr(work), _stream_handle(stream)), "lzf_gpu_size_partition")
+    return perm, cc, cm
+
+
+def host_size_partition(lens, bound, kind):
+    """The same partition over a numpy uint32 array, on the host (no GPU):
+    (perm, class_count, class_max) as numpy uint32 arrays."""
+    import numpy as np
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    perm = np.empty(len(lens), dtype=np.uint32)
+    cc = np.empty(NCLASS + 1, dtype=np.uint32)
+    cm = np.empty(NCLASS + 1, dtype=np.uint32)
+    _check(lib().lzf_host_size_partition(_np_ptr(lens), len(lens), int(bound), int(kind), _np_ptr(perm),
+                                         _np_ptr(cc), _np_ptr(cm)), "lzf_host_size_partition")
+    return perm, cc, cm
+
+
+def mixed_work(count, device):
+    """A scratch tensor for one mixed device call of ``count`` values."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_mixed_work_size(int(count))), dtype=torch.uint8, device=device)
+
+
+def compress_mixed(inp, in_off, in_len, out, out_off, out_cap, out_len, max_in_len, work=None, stream=None):
+    """compress_batch with per-class routing.  Waits once for the 48-byte
+    plan before it launches the class batches; ``work`` (mixed_work) defaults
+    to a fresh tensor and must outlive the stream's work."""
+    n = in_len.numel()
+    if work is None:
+        work = mixed_work(n, inp.device)
+    rc = lib().lzf_gpu_compress_mixed(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off),
+                                      _ptr(out_cap), _ptr(out_len), n, int(max_in_len), _ptr(work),
+                                      _stream_handle(stream))
+    _check(rc, "lzf_gpu_compress_mixed")
+    return work
+
+
+def decompress_mixed(inp, in_off, in_len, out, out_off, out_cap, out_len, err, max_out_cap, work=None,
+                     stream=None):
+    """decompress_batch with per-class routing (see compress_mixed)."""
+    n = in_len.numel()
+    if work is None:
+        work = mixed_work(n, inp.device)
+    rc = lib().lzf_gpu_decompress_mixed(_ptr(inp), _ptr(in_off), _ptr(in_len), _ptr(out), _ptr(out_off),
+                                        _ptr(out_cap), _ptr(out_len), _ptr(err), n, int(max_out_cap),
+                                        _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_decompress_mixed")
+    return work
+
+
+def mixed_last_plan():
+    """This thread's last mixed device call: {"batches", "class_count",
+    "class_max", "route"}, lists of NCLASS + 1 entries.  route: 0 empty;
+    compress 1 lane, 2 table, 3 window64; decompress 1 tokpar, 2 tokpar-far,
+    3 pipe."""
+    cc, cm = (ctypes.c_uint32 * (NCLASS + 1))(), (ctypes.c_uint32 * (NCLASS + 1))()
+    rt = (ctypes.c_int * (NCLASS + 1))()
+    n = lib().lzf_gpu_mixed_last_plan(cc, cm, rt, NCLASS + 1)
+    return {"batches": int(n), "class_count": list(cc), "class_max": list(cm), "route": list(rt)}
+
+
+def host_compress_mixed(inp, in_off, in_len, out, out_off, out_cap, out_len):
+    """host_compress_batch, one uniform host call per size class."""
+    rc = lib().lzf_host_compress_mixed(_np_ptr(inp), _np_ptr(in_off), _np_ptr(in_len), _np_ptr(out),
+                                       _np_ptr(out_off), _np_ptr(out_cap), _np_ptr(out_len), len(in_len))
+    _check(rc, "lzf_host_compress_mixed")
+
+
+def host_decompress_mixed(inp, in_off, in_len, out, out_off, out_cap, out_len, err):
+    rc = lib().lzf_host_decompress_mixed(_np_ptr(inp), _np_ptr(in_off), _np_ptr(in_len), _np_ptr(out),
+                                         _np_ptr(out_off), _np_ptr(out_cap), _np_ptr(out_len), _np_ptr(err),
+                                         len(in_len))
+    _check(rc, "lzf_host_decompress_mixed")
 
 
 def host_register(arr):

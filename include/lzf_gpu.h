@@ -71,6 +71,107 @@ int lzf_gpu_decompress_batch(const uint8_t *in, const uint64_t *in_off, const ui
                              uint32_t max_out_cap, void *stream);
 
 /*
+ * Mixed-size batches.
+ *
+ * The two calls above pick one kernel plan for the whole batch from its
+ * bound, so one large value gives every value of the batch the plan (and the
+ * compress scratch stride) of that size.  The mixed calls below sort the
+ * values into size classes first and run every non-empty class as a batch of
+ * its own, through the same routing, with the class's own largest length as
+ * its bound.  Results are identical to the uniform calls', value by value.
+ * Use them when a batch's sizes spread over more than one class (MSET / MGET
+ * of arbitrary values); a batch of one size gains nothing and pays the
+ * partition.
+ *
+ * Classes (lzf_gpu_size_class; the edges are those of the routing):
+ *   compress, by in_len:    0: <= 4096   1: <= 8192   2: <= 16384
+ *                           3: <= 65536  4: past 65536
+ *   decompress, by out_cap: 0: <= 4096   1: <= 16384  2: past 16384
+ * A value past the caller's bound (in_len > max_in_len, out_cap >
+ * max_out_cap) is refused, reported as class LZF_GPU_NCLASS: out_len 0 (and
+ * err EINVAL on decompress), nothing written to its slot -- the contract of
+ * the uniform calls.
+ */
+#define LZF_GPU_NCLASS           5
+#define LZF_GPU_KIND_COMPRESS    0
+#define LZF_GPU_KIND_DECOMPRESS  1
+
+/* The class of a length (pure host function; LZF_GPU_EARG for a bad kind). */
+int lzf_gpu_size_class(uint32_t len, int kind);
+
+/*
+ * Stable partition of `count` lengths by class, on the device.  perm[k] is
+ * the index of the k-th value in class-major order; inside a class the
+ * original order is kept; values with len > bound come last.  class_count and
+ * class_max have LZF_GPU_NCLASS + 1 entries each (the last: the refused
+ * values): how many values a class holds and the largest length present in
+ * it (0 for an empty class).  `work` is device scratch of
+ * lzf_gpu_size_partition_work_size(count) bytes; every pointer is device
+ * memory; asynchronous on `stream`.  count: anything up to 2^32 - 1.
+ */
+uint64_t lzf_gpu_size_partition_work_size(uint32_t count);
+int lzf_gpu_size_partition(const uint32_t *len, uint32_t count, uint32_t bound, int kind,
+                           uint32_t *perm, uint32_t *class_count, uint32_t *class_max,
+                           void *work, void *stream);
+/* The same partition in host memory; makes no HIP call. */
+int lzf_host_size_partition(const uint32_t *len, uint32_t count, uint32_t bound, int kind,
+                            uint32_t *perm, uint32_t *class_count, uint32_t *class_max);
+
+/*
+ * lzf_gpu_compress_batch / lzf_gpu_decompress_batch with per-class routing.
+ * The arguments mean what they mean there; `work` is device scratch of
+ * lzf_gpu_mixed_work_size(count) bytes that must stay valid until the
+ * stream's work is done.
+ *
+ * THE ONE WAIT: unlike the uniform calls, a mixed call is not fully
+ * asynchronous.  It enqueues the partition on `stream`, copies the 48 bytes
+ * of class counts and maxima to pinned host memory and WAITS for that copy
+ * (and so for everything enqueued on `stream` before it) -- the host needs
+ * them to launch the class batches.  Everything after that is asynchronous
+ * on `stream` as usual.  A mixed call therefore cannot be captured in a HIP
+ * graph.
+ *
+ * Classes that the routing sends to window64 (no scratch, few waves) run on
+ * a library-owned side stream per device, forked from and joined to `stream`
+ * by events, beside the scratch-using classes, which run on `stream` one
+ * after the other, largest class first.  A batch whose values all fall in
+ * one class runs exactly one class batch and no side stream.
+ */
+uint64_t lzf_gpu_mixed_work_size(uint32_t count);
+int lzf_gpu_compress_mixed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                           uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                           uint32_t *out_len, uint32_t count, uint32_t max_in_len,
+                           void *work, void *stream);
+int lzf_gpu_decompress_mixed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                             uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                             uint32_t *out_len, int32_t *err, uint32_t count,
+                             uint32_t max_out_cap, void *work, void *stream);
+/*
+ * The plan of the calling thread's last mixed device call: for k < max (up
+ * to LZF_GPU_NCLASS + 1), class_count[k], class_max[k] and route[k]:
+ * 0 empty (or refused), and for compress 1 lane, 2 table, 3 window64 (4: a
+ * diagnostic generation); for decompress 1 tokpar64, 2 tokpar64-far, 3 pipe.
+ * Returns the number of class batches the call launched.
+ */
+int lzf_gpu_mixed_last_plan(uint32_t *class_count, uint32_t *class_max, int *route, int max);
+
+/*
+ * The host-memory batches (lzf_host_compress_batch / lzf_host_decompress_batch
+ * below, same arguments, host pointers) with per-class routing: the lengths
+ * are partitioned on the host (lzf_host_size_partition, no bound: nothing is
+ * refused), and every non-empty class goes through the uniform host call as
+ * one batch of class-contiguous descriptors -- registered or staged
+ * pipelines, chunking, LZF_GPU_DEVICES and the split as they stand.
+ * lzf_host_last_spread then describes the last class's call.
+ */
+int lzf_host_compress_mixed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                            uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                            uint32_t *out_len, uint32_t count);
+int lzf_host_decompress_mixed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                              uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+                              uint32_t *out_len, int32_t *err, uint32_t count);
+
+/*
  * Decoded-size pre-pass: out_size[i] gets the length lzf_decompress would
  * return for stream i with out_len = out_limit (0 on failure) and err[i]
  * its errno (0, E2BIG or EINVAL in the reference's check order,
