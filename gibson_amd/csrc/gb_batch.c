@@ -9,6 +9,7 @@
 
 #include "../../include/gb_batch.h"
 #include "../../include/lzf_gpu.h"
+#include "gb_policy.h"               /* gb_needcompr: the out_len of src/query.c:384-391 */
 
 /* src/query.c:400-405, applied once per value stored LZF, in request order */
 static void gb_stats_add(gb_stats *s, uint32_t comprlen, uint32_t vlen)
@@ -22,14 +23,18 @@ static void gb_stats_add(gb_stats *s, uint32_t comprlen, uint32_t vlen)
     s->ncompressed++;
 }
 
-/* out_len of src/query.c:384-391: size_t needcompr = vlen - 4, passed as
- * unsigned int, so a value of fewer than 4 bytes gets a wrapped, huge cap.
- * No LZF stream of vlen bytes exceeds vlen + vlen/32 + 1 bytes, so a cap
- * past vlen + vlen/16 + 8 decides exactly like the wrapped one. */
-static uint32_t gb_needcompr(uint32_t vlen)
+/* the STATS fold over the results of a device SET batch (lzf_gpu_set_store):
+ * the same gb_stats_add, once per value stored LZF, in index order */
+int lzf_host_store_stats(const uint8_t *enc, const uint32_t *val_size, const uint32_t *val_len, uint32_t count,
+                         double *compravg, uint64_t *ncompressed)
 {
-    const uint32_t c = (uint32_t)(vlen - 4u), most = vlen + vlen / 16u + 8u;
-    return c < most ? c : most;
+    if (!enc || !val_size || !val_len || !compravg || !ncompressed) return LZF_GPU_EARG;
+    gb_stats s = {*compravg, *ncompressed};
+    for (uint32_t i = 0; i < count; i++)
+        if (enc[i] == GB_ENC_LZF) gb_stats_add(&s, val_size[i], val_len[i]);
+    *compravg = s.compravg;
+    *ncompressed = s.ncompressed;
+    return LZF_GPU_OK;
 }
 
 /* LZF_GPU_MIXED=1 (read per call): the codec batches go through the

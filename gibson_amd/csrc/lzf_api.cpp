@@ -416,6 +416,10 @@ hipError_t launch_decompress(const LzfBatch &b, hipStream_t s)
     }
 }
 
+/* the compress step of the device SET path (lzf_launch_store): the uniform
+ * routed launch over the whole batch; per-class routing would go in here */
+hipError_t store_compress(const LzfBatch &b, hipStream_t s) { return launch_compress(b, s); }
+
 int code_of(hipError_t e)
 {
     if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) return LZF_GPU_ENOMEM;
@@ -781,6 +785,34 @@ int lzf_gpu_kv_frame(const uint8_t *keys, const uint64_t *key_off, const uint32_
     lzf_frame_carve(a, work);
     return lzf_launch_frame(a, (hipStream_t)stream, launch_decompress) == hipSuccess ? LZF_GPU_OK
                                                                                     : LZF_GPU_ELAUNCH;
+}
+
+uint64_t lzf_gpu_set_store_work_size(uint32_t count, uint64_t in_bytes)
+{
+    return lzf_store_work_bytes(count, in_bytes);
+}
+
+int lzf_gpu_set_store(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                      uint32_t count, uint32_t max_in_len, uint64_t in_bytes, uint32_t compression,
+                      uint8_t *store, uint64_t store_cap, uint64_t *store_used,
+                      uint64_t *val_off, uint32_t *val_size, uint8_t *enc, uint32_t *status,
+                      void *work, void *stream)
+{
+    if (!count || !in || !in_off || !in_len || !store || !store_used || !val_off || !val_size || !enc ||
+        !status || !work)
+        return LZF_GPU_EARG;
+    if (max_in_len > LZF_GPU_MAX_VALUE || !store_cap) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfStoreArgs a{};
+    a.in = in; a.in_off = in_off; a.in_len = in_len;
+    a.count = count; a.max_in_len = max_in_len; a.compression = compression;
+    a.in_bytes = in_bytes;
+    a.store = store; a.store_cap = store_cap; a.store_used = store_used;
+    a.val_off = val_off; a.val_size = val_size; a.enc = enc; a.status = status;
+    lzf_store_carve(a, work);
+    const hipError_t e = lzf_launch_store(a, (hipStream_t)stream, store_compress);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
 }
 
 int lzf_gpu_selfcheck(void)

@@ -53,6 +53,26 @@ struct LzfFrameArgs {
     uint8_t *w_skip;
 };
 
+/* the device SET path (lzf_store.hip); device pointers */
+struct LzfStoreArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;
+    const uint32_t *in_len;
+    uint32_t count, max_in_len, compression;
+    uint64_t in_bytes;
+    uint8_t *store;
+    uint64_t store_cap;
+    uint64_t *store_used;
+    uint64_t *val_off;
+    uint32_t *val_size;
+    uint8_t *enc;
+    uint32_t *status;
+    /* work area (lzf_store_carve) */
+    uint64_t *w_state, *w_slot_off, *w_tile;
+    uint32_t *w_len, *w_cap, *w_out;
+    uint8_t *w_slots;
+};
+
 /* compress scratch of the lane generation (lzf_lane.hip), device pointers:
  * per value cstride u16 cand words and bstride u32 inserted-bitmap words */
 struct LzfLaneScratch {
@@ -112,6 +132,12 @@ hipError_t lzf_launch_frame(LzfFrameArgs &a, hipStream_t s,
 size_t lzf_frame_work_bytes(uint32_t count);
 void lzf_frame_carve(LzfFrameArgs &a, void *work);
 const char *lzf_compress_kernel_name(void);
+/* the device SET path: plan, `compress` over the candidates' scratch slots,
+ * sizes and the store decision, the dense pack (lzf_store.hip) */
+hipError_t lzf_launch_store(LzfStoreArgs &a, hipStream_t s,
+                            hipError_t (*compress)(const LzfBatch &, hipStream_t));
+uint64_t lzf_store_work_bytes(uint32_t count, uint64_t in_bytes);
+void lzf_store_carve(LzfStoreArgs &a, void *work);
 /* value moves between mapped host memory and device arenas (lzf_hostio.hip):
  * len[k] (at least min_len) bytes from src + src_off[k] to dst + dst_off[k] */
 hipError_t lzf_launch_move(const uint8_t *src, const uint64_t *src_off, uint8_t *dst, const uint64_t *dst_off,

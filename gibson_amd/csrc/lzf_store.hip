@@ -1,0 +1,533 @@
+/*
+ * lzf_store.hip -- the device SET path: gbSingleSet's store decision and the
+ * dense copy into the store (src/query.c:384-417), for a whole batch, with the
+ * values staying in HBM (lzf_gpu_set_store, include/lzf_gpu.h).
+ *
+ * The reference compresses a value above the `compression` threshold into
+ * lzf_buffer with out_len = vlen - 4 (src/query.c:389-391), stores the stream
+ * when there is one and the plain bytes when there is none (zmemdup,
+ * src/query.c:409) and records item->size and item->encoding.  Here, on one
+ * stream, with no host wait:
+ *
+ *   1. plan: per value whether it is a candidate (in_len > compression, within
+ *      max_in_len) and its cap (gb_needcompr, gb_policy.h); the exclusive scan
+ *      of the caps gives every candidate a scratch slot of exactly cap bytes
+ *      (at most in_len + 8).  The slots must fit in in_bytes + 8 * count
+ *      (LZF_STORE_EWORK otherwise).  A work copy of the lengths has 0 for
+ *      every value that is not a candidate.
+ *   2. compress: the routed compress launch over all `count` values with the
+ *      work lengths (a 0-length value: out_len 0, src/lzf_c.c:131), handed in
+ *      as a function pointer.
+ *   3. size: val_size (the stream length, or in_len where there is no stream)
+ *      and enc; the 64-bit exclusive scan of the sizes from base = *store_used
+ *      gives val_off; base + total must fit in store_cap (LZF_STORE_FULL).
+ *   4. pack: the stored bytes of every value to store + val_off[i].
+ *
+ * Scans (steps 1 and 3) are reduce-then-scan over tiles of 1024 values: tile
+ * sums (wave prefix sums by __shfl_up, the 4 wave totals through LDS), one
+ * workgroup's running scan over the tile sums (any tile count), and a second
+ * pass that writes the absolute offsets.  No workgroup waits for another.
+ *
+ * Pack layout.  Work is balanced by DESTINATION bytes: the packed range
+ * [store + base, store + base + total) is cut into tiles of ST_PACK_TILE bytes
+ * whose starts are 16-byte aligned absolute addresses, so no two workgroups
+ * ever touch one 16-byte granule; workgroups take tiles grid-stride (the grid
+ * is fixed at launch, the tile count is computed on the device).  A workgroup
+ * finds the value that holds its tile's first byte by a search in val_off for
+ * the LAST index with val_off[i] <= p, which steps over runs of zero-size
+ * values, whose offsets tie (all its threads probe at once: 256 entries per
+ * round).  It copies the offsets and sources of the tile's values (up to 512)
+ * into LDS, and every lane finds the value of a granule there the same way; a
+ * tile of more values (runs of tiny ones) looks them up in HBM.  A granule
+ * that lies wholly inside one value moves as one 16-byte load and one aligned
+ * 16-byte store, whatever the source's alignment (an unaligned global load;
+ * LZF_GPU_STORE_PACK=realign: two aligned loads realigned in registers).
+ * Value heads, tails and values shorter than a granule are gathered byte by
+ * byte into one aligned 16-byte store, one lane per granule, after the tile's
+ * whole granules.
+ *
+ * The kernels are helpers of this translation unit, not part of the library's
+ * routed kernel set: they have internal linkage (anonymous namespace).
+ */
+#include <stdlib.h>
+#include <string.h>
+
+#include "lzf_internal.h"
+#include "gb_policy.h"
+#include "../../include/lzf_gpu.h"
+
+#define ST_BLOCK 256u
+#define ST_PER   4u
+#define ST_TILE  (ST_BLOCK * ST_PER)      /* values per scan tile */
+#define ST_WAVES (ST_BLOCK / 64u)
+/* destination bytes per pack tile (a multiple of 16 * ST_BLOCK = 4096, so
+ * every lane of a workgroup has the same number of granules).  256 K x 4 KiB
+ * json, 500 MB packed: the pack kernel takes 467 us at 16 KiB and 300 us at
+ * 64 KiB (a plain copy of the same bytes: 184 us); 4 KiB is slower again and
+ * 256 KiB no faster (profiles/r08/store/): per tile the workgroup pays the
+ * search and the table fill before it copies, and past 64 KiB a small batch
+ * would sit on few workgroups */
+#define ST_PACK_TILE 65536u
+#define ST_PACK_GRID 2048u                /* 256 CUs x 8 workgroups */
+
+static inline uint32_t st_tiles(uint32_t count)
+{
+    return (uint32_t)(((uint64_t)count + ST_TILE - 1u) / ST_TILE);
+}
+
+/* the scratch slots' room: in_bytes + 8 * count, saturating */
+static __host__ __device__ inline uint64_t st_slot_room(uint64_t in_bytes, uint32_t count)
+{
+    const uint64_t r = in_bytes + 8ull * count;
+    return r < in_bytes ? ~0ull : r;
+}
+
+namespace {
+
+/* state words of the work area */
+enum { ST_EWORK = 0, ST_BASE = 1, ST_TOTAL = 2, ST_STATUS = 3 };
+
+__device__ inline uint64_t st_shfl_up64(uint64_t x, int d)
+{
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, d, 64);
+    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), d, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+/* block-wide exclusive scan of one u64 per thread: an inclusive wave scan,
+ * then the totals of the waves before this one; sw: ST_WAVES words of LDS */
+__device__ inline uint64_t st_block_excl(uint64_t x, uint64_t *sw, uint64_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t inc = x;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = st_shfl_up64(inc, d);
+        if (lane >= (uint32_t)d) inc += o;
+    }
+    if (lane == 63u) sw[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0ull, all = 0ull;
+    for (uint32_t w = 0; w < ST_WAVES; w++) {
+        if (w < wave) before += sw[w];
+        all += sw[w];
+    }
+    __syncthreads();
+    *total = all;
+    return before + inc - x;
+}
+
+/* what the scan of step 1 (SIZE false: the cap of a candidate, 0 otherwise)
+ * and of step 3 (SIZE true: the stored size) adds up */
+template <bool SIZE>
+__device__ inline uint64_t st_item(const LzfStoreArgs &a, uint64_t i, bool ework)
+{
+    const uint32_t len = a.in_len[i];
+    if (SIZE) {
+        const uint32_t got = a.w_out[i];
+        return ework ? 0ull : got ? got : len;
+    }
+    /* src/query.c:389, strict; past max_in_len: not compressed, stored plain */
+    return (len > a.compression && len <= a.max_in_len) ? gb_needcompr(len) : 0u;
+}
+
+template <bool SIZE>
+__global__ __launch_bounds__(ST_BLOCK) void lzf_store_reduce_kernel(LzfStoreArgs a)
+{
+    __shared__ uint64_t sw[ST_WAVES];
+    const bool ework = SIZE && a.w_state[ST_EWORK] != 0ull;
+    const uint64_t first = (uint64_t)blockIdx.x * ST_TILE + threadIdx.x * ST_PER;
+    uint64_t s = 0ull;
+#pragma unroll
+    for (uint32_t k = 0; k < ST_PER; k++)
+        if (first + k < a.count) s += st_item<SIZE>(a, first + k, ework);
+    uint64_t tot;
+    (void)st_block_excl(s, sw, &tot);
+    if (threadIdx.x == 0u) a.w_tile[blockIdx.x] = tot;
+}
+
+/* one workgroup: the exclusive scan of the tile sums in place, in pieces of
+ * ST_BLOCK with a running carry, and the batch-wide decision */
+template <bool SIZE>
+__global__ __launch_bounds__(ST_BLOCK) void lzf_store_carry_kernel(LzfStoreArgs a, uint32_t ntile)
+{
+    __shared__ uint64_t sw[ST_WAVES];
+    uint64_t run = 0ull;
+    for (uint32_t c = 0; c < ntile; c += ST_BLOCK) {
+        const uint32_t i = c + threadIdx.x;
+        const uint64_t x = i < ntile ? a.w_tile[i] : 0ull;
+        uint64_t tot;
+        const uint64_t o = st_block_excl(x, sw, &tot);
+        if (i < ntile) a.w_tile[i] = run + o;
+        run += tot;
+    }
+    if (threadIdx.x != 0u) return;
+    if (!SIZE) {
+        a.w_state[ST_EWORK] = run > st_slot_room(a.in_bytes, a.count) ? 1ull : 0ull;
+        return;
+    }
+    const uint64_t base = *a.store_used, end = base + run;
+    uint32_t st = LZF_STORE_OK;
+    if (a.w_state[ST_EWORK]) st = LZF_STORE_EWORK;
+    else if (end < base || end > a.store_cap) st = LZF_STORE_FULL;
+    a.w_state[ST_BASE] = base;
+    a.w_state[ST_TOTAL] = st == LZF_STORE_OK ? run : 0ull;
+    a.w_state[ST_STATUS] = st;
+    *a.status = st;
+    if (st == LZF_STORE_OK) *a.store_used = end;
+}
+
+template <bool SIZE>
+__global__ __launch_bounds__(ST_BLOCK) void lzf_store_write_kernel(LzfStoreArgs a)
+{
+    __shared__ uint64_t sw[ST_WAVES];
+    const bool ework = a.w_state[ST_EWORK] != 0ull;
+    const bool refused = SIZE && a.w_state[ST_STATUS] != 0ull;
+    const uint64_t first = (uint64_t)blockIdx.x * ST_TILE + threadIdx.x * ST_PER;
+    uint64_t v[ST_PER], s = 0ull;
+#pragma unroll
+    for (uint32_t k = 0; k < ST_PER; k++) {
+        v[k] = first + k < a.count ? st_item<SIZE>(a, first + k, ework) : 0ull;
+        s += v[k];
+    }
+    uint64_t tot;
+    uint64_t o = st_block_excl(s, sw, &tot) + a.w_tile[blockIdx.x];
+    if (SIZE) o += a.w_state[ST_BASE];
+#pragma unroll
+    for (uint32_t k = 0; k < ST_PER; k++) {
+        const uint64_t i = first + k;
+        if (i >= a.count) break;
+        if (SIZE) {
+            /* a refused batch: nothing stored, every item skipped by kv_frame */
+            a.val_off[i] = refused ? a.w_state[ST_BASE] : o;
+            a.val_size[i] = refused ? 0u : (uint32_t)v[k];
+            a.enc[i] = refused ? (uint8_t)LZF_ENC_NULL : a.w_out[i] ? (uint8_t)LZF_ENC_LZF : (uint8_t)LZF_ENC_PLAIN;
+        } else {
+            /* on EWORK no slot is used: every value goes in with length 0 */
+            const uint32_t cap = ework ? 0u : (uint32_t)v[k];
+            a.w_slot_off[i] = ework ? 0ull : o;
+            a.w_cap[i] = cap;
+            a.w_len[i] = cap ? a.in_len[i] : 0u;
+        }
+        o += v[k];
+    }
+}
+
+/* the last index i in [lo, hi) with off[i] <= p; needs off[lo] <= p.  Among
+ * equal offsets (zero-size values) it is the last one: the value that holds
+ * byte p, when any does */
+__device__ inline uint32_t st_find(const uint64_t *__restrict__ off, uint32_t lo, uint32_t hi, uint64_t p)
+{
+    while (hi - lo > 1u) {
+        const uint32_t m = lo + ((hi - lo) >> 1);
+        if (off[m] <= p) lo = m;
+        else hi = m;
+    }
+    return lo;
+}
+
+/* how many threads of the workgroup say yes; sc: ST_WAVES words of LDS */
+__device__ inline uint32_t st_block_count(uint32_t wave_yes, uint32_t *sc)
+{
+    if ((threadIdx.x & 63u) == 0u) sc[threadIdx.x >> 6] = wave_yes;
+    __syncthreads();
+    uint32_t n = 0u;
+    for (uint32_t w = 0; w < ST_WAVES; w++) n += sc[w];
+    __syncthreads();
+    return n;
+}
+
+/* st_find by the whole workgroup: every round the threads probe ST_BLOCK
+ * evenly spaced entries of [lo, hi) at once and the range shrinks to one
+ * stride, so 2^32 entries take four dependent loads, not 32.  The same
+ * result in every thread */
+__device__ inline uint32_t st_find_block(const uint64_t *__restrict__ off, uint32_t lo, uint32_t hi, uint64_t p,
+                                         uint32_t *sc)
+{
+    while (hi - lo > 1u) {
+        const uint32_t step = (uint32_t)(((uint64_t)(hi - lo) + ST_BLOCK - 1u) / ST_BLOCK);
+        const uint64_t i = lo + (uint64_t)threadIdx.x * step;
+        const bool yes = i < hi && off[i] <= p;       /* true for the threads up to the one that holds p */
+        const uint32_t c = st_block_count((uint32_t)__popcll(__ballot(yes)), sc);
+        lo += (c ? c - 1u : 0u) * step;
+        hi = (uint64_t)lo + step < hi ? lo + step : hi;
+    }
+    return lo;
+}
+
+/* 16 bytes at s (any alignment) from the two aligned 16-byte pieces around it;
+ * the second piece is read only when s is not aligned, and then holds byte
+ * s + 15, so neither load leaves the pages the 16 bytes lie in */
+__device__ inline uint4 st_ld16_realign(const uint8_t *s)
+{
+    const uint32_t k = (uint32_t)((uintptr_t)s & 15u);
+    const uint4 *q = (const uint4 *)(s - k);
+    const uint4 a = q[0];
+    if (!k) return a;
+    const uint4 b = q[1];
+    const uint32_t ws = k >> 2, sh = k & 3u;
+    const uint32_t x0 = ws == 0u ? a.x : ws == 1u ? a.y : ws == 2u ? a.z : a.w;
+    const uint32_t x1 = ws == 0u ? a.y : ws == 1u ? a.z : ws == 2u ? a.w : b.x;
+    const uint32_t x2 = ws == 0u ? a.z : ws == 1u ? a.w : ws == 2u ? b.x : b.y;
+    const uint32_t x3 = ws == 0u ? a.w : ws == 1u ? b.x : ws == 2u ? b.y : b.z;
+    const uint32_t x4 = ws == 0u ? b.x : ws == 1u ? b.y : ws == 2u ? b.z : b.w;
+    return make_uint4(__builtin_amdgcn_alignbyte(x1, x0, sh), __builtin_amdgcn_alignbyte(x2, x1, sh),
+                      __builtin_amdgcn_alignbyte(x3, x2, sh), __builtin_amdgcn_alignbyte(x4, x3, sh));
+}
+
+__device__ inline uint4 st_ld16(const uint8_t *s)
+{
+    uint4 v;
+    __builtin_memcpy(&v, s, 16);
+    return v;
+}
+
+/* where value i's stored bytes come from, as one word: the offset in the
+ * scratch slots (top bit set) or in the input arena */
+#define ST_FROM_SLOT (1ull << 63)
+__device__ inline uint64_t st_source(const LzfStoreArgs &a, uint32_t i)
+{
+    return a.w_out[i] ? a.w_slot_off[i] | ST_FROM_SLOT : a.in_off[i];
+}
+
+__device__ inline const uint8_t *st_source_ptr(const LzfStoreArgs &a, uint64_t from)
+{
+    return (from & ST_FROM_SLOT ? a.w_slots : a.in) + (from & ~ST_FROM_SLOT);
+}
+
+/* The value that holds byte p of the store (an offset from the store's start),
+ * for the values [i0, i1) of one tile: its first byte vo, its end ve -- the
+ * next value's offset, the packing is dense -- and its source.  From the
+ * arrays in HBM: */
+struct StMapGlobal {
+    const LzfStoreArgs &a;
+    uint32_t i0, i1;
+    uint64_t end;                      /* base + total */
+    __device__ inline void at(uint64_t p, uint64_t &vo, uint64_t &ve, const uint8_t *&src) const
+    {
+        const uint32_t i = st_find(a.val_off, i0, i1, p);
+        vo = a.val_off[i];
+        ve = i + 1u < a.count ? a.val_off[i + 1u] : end;
+        src = st_source_ptr(a, st_source(a, i));
+    }
+};
+
+/* ... and from the tile's copy of them in LDS (off: n + 1 entries), which
+ * takes the dependent loads from HBM out of every granule's way */
+struct StMapLds {
+    const LzfStoreArgs &a;
+    const uint64_t *off, *from;
+    uint32_t n;
+    __device__ inline void at(uint64_t p, uint64_t &vo, uint64_t &ve, const uint8_t *&src) const
+    {
+        const uint32_t k = st_find(off, 0u, n, p);
+        vo = off[k];
+        ve = off[k + 1u];
+        src = st_source_ptr(a, from[k]);
+    }
+};
+
+/* one granule that is not wholly inside one value -- a value's head and its
+ * neighbour's tail, values shorter than a granule, the packed range's first
+ * and last granule: its bytes [q0, q1) gathered byte by byte, every load in
+ * flight at once, then one aligned 16-byte store (byte stores for a partial
+ * granule).  Absolute addresses; sa: the store's address */
+template <typename Map>
+__device__ inline void st_pack_edge(const LzfStoreArgs &a, const Map &m, uint64_t sa, uint64_t g, uint64_t lo,
+                                    uint64_t hi)
+{
+    const uint64_t q0 = g > lo ? g : lo, q1 = g + 16u < hi ? g + 16u : hi;
+    uint64_t vo = 0ull, ve = 0ull;
+    const uint8_t *src = nullptr;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; j++) {
+        if (g + j < q0 || g + j >= q1) continue;
+        const uint64_t p = g + j - sa;
+        if (p >= ve) m.at(p, vo, ve, src);                /* the next value that has bytes */
+        w[j >> 2] |= (uint32_t)src[p - vo] << (8u * (j & 3u));
+    }
+    if (q1 - q0 == 16u) {
+        *(uint4 *)(a.store + (g - sa)) = make_uint4(w[0], w[1], w[2], w[3]);
+        return;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; j++)
+        if (g + j >= q0 && g + j < q1) a.store[g + j - sa] = (uint8_t)(w[j >> 2] >> (8u * (j & 3u)));
+}
+
+/* one tile: bytes [lo, hi), absolute addresses like the tile's 16-byte
+ * aligned start ta.  Four granules per lane and pass, the loads of a pass
+ * before its stores; a granule inside one value is one 16-byte load and one
+ * aligned 16-byte store.  The other granules: in place (EDGES), or left to
+ * the caller */
+template <bool REALIGN, bool EDGES, typename Map>
+__device__ inline void st_pack_tile(const LzfStoreArgs &a, const Map &m, uint64_t sa, uint64_t ta, uint64_t lo,
+                                    uint64_t hi)
+{
+    for (uint64_t gb = ta + 16ull * threadIdx.x; gb < hi; gb += 64ull * ST_BLOCK) {
+        uint4 v[4];
+        uint32_t how[4];               /* 0: nothing, 1: v is the granule, 2: not inside one value */
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++) {
+            const uint64_t g = gb + 16ull * ST_BLOCK * u;
+            how[u] = 0u;
+            if (g < lo || g + 16u > hi) {                 /* a partial granule, or past the tile */
+                if (g + 16u > lo && g < hi) how[u] = 2u;
+                continue;
+            }
+            uint64_t vo, ve;
+            const uint8_t *src;
+            m.at(g - sa, vo, ve, src);
+            if (ve < g + 16u - sa) {
+                how[u] = 2u;
+                continue;
+            }
+            const uint8_t *s = src + (g - sa - vo);
+            v[u] = REALIGN ? st_ld16_realign(s) : st_ld16(s);
+            how[u] = 1u;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++)
+            if (how[u] == 1u) *(uint4 *)(a.store + (gb + 16ull * ST_BLOCK * u - sa)) = v[u];
+        if (EDGES) {
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; u++)
+                if (how[u] == 2u) st_pack_edge(a, m, sa, gb + 16ull * ST_BLOCK * u, lo, hi);
+        }
+    }
+}
+
+/* values of a tile kept in LDS; a tile of more (runs of tiny values) looks
+ * them up in HBM */
+#define ST_LDS_VALS 512u
+
+template <bool REALIGN>
+__global__ __launch_bounds__(ST_BLOCK) void lzf_store_pack_kernel(LzfStoreArgs a, uint32_t tile)
+{
+    __shared__ uint64_t s_off[ST_LDS_VALS + 1u], s_from[ST_LDS_VALS];
+    __shared__ uint32_t sc[ST_WAVES];
+    const uint64_t total = a.w_state[ST_TOTAL];
+    if (!total) return;                                   /* refused, or nothing to store */
+    /* absolute addresses: the packed range [d0, d1), tiles from a0 (which may
+     * lie up to 15 bytes before d0: nothing is accessed there) */
+    const uint64_t sa = (uint64_t)(uintptr_t)a.store, d0 = sa + a.w_state[ST_BASE], d1 = d0 + total;
+    const uint64_t a0 = d0 & ~15ull;
+    const uint64_t ntile = (d1 - a0 + tile - 1u) / tile;
+    const uint64_t *__restrict__ voff = a.val_off;
+    for (uint64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
+        const uint64_t ta = a0 + t * tile;
+        const uint64_t lo = ta > d0 ? ta : d0, hi = ta + tile < d1 ? ta + tile : d1;
+        /* i0: the value that holds byte lo */
+        const uint32_t i0 = st_find_block(voff, 0u, a.count, lo - sa, sc);
+        __syncthreads();                                  /* the tile before is done with the table */
+        /* the ST_LDS_VALS + 1 entries from i0 into LDS, and n: how many of
+         * them start at or before the tile's last byte -- the tile's values
+         * [i0, i0 + n), entry n being the end of the last one */
+        uint32_t yes = 0u;
+        for (uint32_t k = threadIdx.x; k < ST_LDS_VALS + ST_BLOCK; k += ST_BLOCK) {
+            const uint64_t i = (uint64_t)i0 + k;
+            const bool in = k <= ST_LDS_VALS && i < a.count;
+            const uint64_t o = in ? voff[i] : d1 - sa;
+            if (k <= ST_LDS_VALS) s_off[k] = o;
+            if (in && k < ST_LDS_VALS) s_from[k] = st_source(a, (uint32_t)i);
+            yes += (uint32_t)__popcll(__ballot(in && o <= hi - 1u - sa));
+        }
+        const uint32_t n = st_block_count(yes, sc);       /* its barrier: the table is written */
+        if (n > ST_LDS_VALS) {                            /* a run of tiny values: look them up in HBM */
+            const uint32_t i1 = st_find_block(voff, i0, a.count, hi - 1u - sa, sc) + 1u;
+            st_pack_tile<REALIGN, true>(a, StMapGlobal{a, i0, i1, d1 - sa}, sa, ta, lo, hi);
+            continue;
+        }
+        const StMapLds m{a, s_off, s_from, n};
+        st_pack_tile<REALIGN, false>(a, m, sa, ta, lo, hi);
+        /* the granules not inside one value are those that hold a cut -- a
+         * value's start, or the range's end -- at an address that is no
+         * multiple of 16: one lane per cut, so a wave works on 64 of them at
+         * once.  Cuts in one granule are neighbours in the table: the first
+         * takes the granule */
+        for (uint32_t k = threadIdx.x; k <= n; k += ST_BLOCK) {
+            const uint64_t c = sa + s_off[k];
+            if (!(c & 15ull) || c < lo || c > hi) continue;
+            const uint64_t g = c & ~15ull;
+            if (k) {
+                const uint64_t pc = sa + s_off[k - 1u];
+                if ((pc & 15ull) && (pc & ~15ull) == g && pc >= lo) continue;
+            }
+            st_pack_edge(a, m, sa, g, lo, hi);
+        }
+    }
+}
+
+/* LZF_GPU_STORE_TILE_KB (diagnostics, read per launch): the pack tile in KiB,
+ * a multiple of 4 up to 1024 */
+uint32_t st_pack_tile()
+{
+    const char *e = getenv("LZF_GPU_STORE_TILE_KB");
+    if (e) {
+        const unsigned long kb = strtoul(e, nullptr, 10);
+        if (kb >= 4u && kb <= 1024u && kb % 4u == 0u) return (uint32_t)kb << 10;
+    }
+    return ST_PACK_TILE;
+}
+
+/* LZF_GPU_STORE_PACK=realign (diagnostics): aligned loads realigned in
+ * registers instead of unaligned global loads */
+bool st_pack_realign()
+{
+    const char *e = getenv("LZF_GPU_STORE_PACK");
+    return e && !strcmp(e, "realign");
+}
+
+}  // namespace
+
+uint64_t lzf_store_work_bytes(uint32_t count, uint64_t in_bytes)
+{
+    /* state (8 x u64) | slot_off (u64) | tile sums (u64 per tile) | len, cap,
+     * out_len (u32) | the slots, and 16 bytes the realigning loads may read
+     * past them; room to align the caller's pointer */
+    const uint64_t fixed = 64u + (uint64_t)count * (8u + 3u * 4u) + (uint64_t)st_tiles(count) * 8u + 16u + 16u;
+    const uint64_t room = st_slot_room(in_bytes, count);
+    return room > ~0ull - fixed ? ~0ull : room + fixed;
+}
+
+void lzf_store_carve(LzfStoreArgs &a, void *work)
+{
+    uint8_t *w = (uint8_t *)(((uintptr_t)work + 15u) & ~(uintptr_t)15u);
+    a.w_state = (uint64_t *)w;            w += 64;
+    a.w_slot_off = (uint64_t *)w;         w += (size_t)a.count * 8;
+    a.w_tile = (uint64_t *)w;             w += (size_t)st_tiles(a.count) * 8;
+    a.w_len = (uint32_t *)w;              w += (size_t)a.count * 4;
+    a.w_cap = (uint32_t *)w;              w += (size_t)a.count * 4;
+    a.w_out = (uint32_t *)w;              w += (size_t)a.count * 4;
+    a.w_slots = w;
+}
+
+hipError_t lzf_launch_store(LzfStoreArgs &a, hipStream_t s, hipError_t (*compress)(const LzfBatch &, hipStream_t))
+{
+    const uint32_t nt = st_tiles(a.count);
+    hipLaunchKernelGGL(lzf_store_reduce_kernel<false>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_store_carry_kernel<false>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_store_write_kernel<false>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    /* a batch with no candidate at all (max_in_len 0) is not compressed */
+    if ((e = hipMemsetAsync(a.w_out, 0, (size_t)a.count * sizeof(uint32_t), s)) != hipSuccess) return e;
+    if (a.max_in_len) {
+        LzfBatch b{a.in, a.in_off, a.w_len, a.w_slots, a.w_slot_off, a.w_cap, a.w_out, nullptr, a.count, a.max_in_len};
+        if ((e = compress(b, s)) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(lzf_store_reduce_kernel<true>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_store_carry_kernel<true>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_store_write_kernel<true>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    /* the grid from the host's bound on the packed bytes; the kernel strides
+     * over the tiles there really are */
+    const uint32_t tile = st_pack_tile();
+    const uint64_t most = st_slot_room(a.in_bytes, a.count) / tile + 2u;
+    const uint32_t grid = (uint32_t)(most < ST_PACK_GRID ? most : ST_PACK_GRID);
+    if (st_pack_realign())
+        hipLaunchKernelGGL(lzf_store_pack_kernel<true>, dim3(grid), dim3(ST_BLOCK), 0, s, a, tile);
+    else
+        hipLaunchKernelGGL(lzf_store_pack_kernel<false>, dim3(grid), dim3(ST_BLOCK), 0, s, a, tile);
+    return hipGetLastError();
+}

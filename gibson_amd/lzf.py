@@ -49,11 +49,17 @@ EXPORTS = (
     "lzf_gpu_mixed_last_plan",
     "lzf_host_compress_mixed",
     "lzf_host_decompress_mixed",
+    "lzf_gpu_set_store_work_size",
+    "lzf_gpu_set_store",
+    "lzf_host_store_stats",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
 NCLASS = 5
 KIND_COMPRESS, KIND_DECOMPRESS = 0, 1
+
+# *status of set_store (include/lzf_gpu.h)
+STORE_OK, STORE_FULL, STORE_EWORK = 0, 1, 2
 
 # item encodings (src/net.h:274-278) and the MGET reply code (src/query.h:71)
 ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
@@ -159,6 +165,8 @@ def _load(path):
     L.lzf_gpu_parse_device_list.argtypes = [ctypes.c_char_p, ctypes.c_int, vp, ctypes.c_int]
     if hasattr(L, "lzf_gpu_compress_mixed"):
         _bind_mixed(L)
+    if hasattr(L, "lzf_gpu_set_store"):
+        _bind_store(L)
     del i32
     _LOADED[path] = L
     return L
@@ -189,6 +197,18 @@ def _bind_mixed(L):
     L.lzf_host_compress_mixed.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32]
     L.lzf_host_decompress_mixed.restype = ctypes.c_int
     L.lzf_host_decompress_mixed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32]
+
+
+def _bind_store(L):
+    """The device SET path; like the mixed calls, absent from an older build
+    given by LZF_HIP_LIB (the helpers below then raise AttributeError)."""
+    u32, u64, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
+    L.lzf_gpu_set_store_work_size.restype = u64
+    L.lzf_gpu_set_store_work_size.argtypes = [u32, u64]
+    L.lzf_gpu_set_store.restype = ctypes.c_int
+    L.lzf_gpu_set_store.argtypes = [vp, vp, vp, u32, u32, u64, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.lzf_host_store_stats.restype = ctypes.c_int
+    L.lzf_host_store_stats.argtypes = [vp, vp, vp, u32, vp, vp]
 
 
 def selfcheck():
@@ -399,6 +419,59 @@ def host_decompress_mixed(inp, in_off, in_len, out, out_off, out_cap, out_len, e
                                          _np_ptr(out_off), _np_ptr(out_cap), _np_ptr(out_len), _np_ptr(err),
                                          len(in_len))
     _check(rc, "lzf_host_decompress_mixed")
+
+
+# ---- SET batch into a device-resident store ---------------------------------
+
+def set_store_work(count, in_bytes, device):
+    """A scratch tensor for one set_store call of ``count`` values whose
+    lengths sum to at most ``in_bytes``."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_set_store_work_size(int(count), int(in_bytes))), dtype=torch.uint8,
+                       device=device)
+
+
+def set_store(inp, in_off, in_len, compression, max_in_len, in_bytes, store, store_used, val_off, val_size, enc,
+              status, work=None, stream=None):
+    """gbSingleSet for a batch, the values staying on the device: compress
+    every value longer than ``compression``, decide LZF / PLAIN, and pack the
+    stored bytes densely into ``store`` from ``store_used[0]`` on, which is
+    advanced.  Writes the arrays kv_frame reads (pass ``in_len`` there as
+    val_len).  Tensors on one device: inp/store/enc uint8, in_off/val_off/
+    store_used (1 element) int64, in_len/val_size/status (1 element) int32.
+    status: STORE_OK, or STORE_FULL / STORE_EWORK with the whole batch refused
+    (every enc ENC_NULL).  No host wait; ``work`` (set_store_work) defaults to
+    a fresh tensor and must outlive the stream's work."""
+    n = in_len.numel()
+    if work is None:
+        work = set_store_work(n, in_bytes, inp.device)
+    rc = lib().lzf_gpu_set_store(_ptr(inp), _ptr(in_off), _ptr(in_len), n, int(max_in_len), int(in_bytes),
+                                 int(compression), _ptr(store), int(store.numel()), _ptr(store_used), _ptr(val_off),
+                                 _ptr(val_size), _ptr(enc), _ptr(status), _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_set_store")
+    return work
+
+
+def store_stats(enc, val_size, val_len, compravg=0.0, ncompressed=0):
+    """lzf_host_store_stats(): the STATS running mean (src/query.c:400-405)
+    folded over a set_store batch's results in request order, on the host.
+    Takes numpy arrays or tensors (copied to the host); returns
+    (compravg, ncompressed)."""
+    import numpy as np
+
+    def host(a, dt):
+        if hasattr(a, "cpu"):
+            a = a.cpu().numpy()
+        a = np.ascontiguousarray(a)
+        return a.view(dt) if a.dtype.itemsize == np.dtype(dt).itemsize else a.astype(dt)
+
+    e, s, v = host(enc, np.uint8), host(val_size, np.uint32), host(val_len, np.uint32)
+    if not len(e) == len(s) == len(v):
+        raise ValueError("store_stats: arrays of different lengths")
+    avg, n = ctypes.c_double(compravg), ctypes.c_uint64(ncompressed)
+    _check(lib().lzf_host_store_stats(_np_ptr(e), _np_ptr(s), _np_ptr(v), len(e), ctypes.byref(avg),
+                                      ctypes.byref(n)), "lzf_host_store_stats")
+    return avg.value, n.value
 
 
 def host_register(arr):

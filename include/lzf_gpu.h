@@ -300,6 +300,56 @@ int lzf_gpu_kv_frame(const uint8_t *keys, const uint64_t *key_off, const uint32_
                      uint8_t *frame, uint64_t max_response, uint64_t *frame_len, void *work,
                      void *stream);
 
+/*
+ * SET batch into a device-resident store (the write side of lzf_gpu_kv_frame).
+ *
+ * gbSingleSet for a whole batch, the values never leaving HBM: the store
+ * decision (src/query.c:389-397), the dense copy into the store
+ * (src/query.c:409) and the item's size and encoding (src/query.c:408-417).
+ * Value i is in[in_off[i] .. +in_len[i]).  It is compressed iff
+ * in_len[i] > compression (strict, src/query.c:389), with the reference's
+ * out_len = vlen - 4 (for a value shorter than 4 bytes the wrapped size_t:
+ * no limit, so a 1-byte value at compression 0 is stored LZF as 2 bytes).
+ *   a stream:      enc[i] = LZF_ENC_LZF,   val_size[i] = the stream's length;
+ *   no stream (0): enc[i] = LZF_ENC_PLAIN, val_size[i] = in_len[i], the input
+ *                  bytes stored -- also for in_len[i] == 0 (size 0) and for a
+ *                  value past max_in_len (a caller that under-states the bound).
+ * The original length of an LZF item is in_len[i]: pass in_len to
+ * lzf_gpu_kv_frame as val_len.
+ *
+ * The stored bytes are packed densely, in request order, from base =
+ * *store_used: val_off[i] = base + the sizes before i (64-bit), at
+ * store + val_off[i].  On success *store_used = base + the batch's bytes and
+ * *status = LZF_STORE_OK, so consecutive calls on one stream append to one
+ * arena.  The batch is refused as a whole when base + its bytes exceed
+ * store_cap (LZF_STORE_FULL) or when the compress slots do not fit in
+ * in_bytes + 8 * count bytes (LZF_STORE_EWORK: in_bytes, the caller's upper
+ * bound on the sum of in_len, was under-stated).  Then *store_used is
+ * unchanged, no byte of store is written, every enc[i] is LZF_ENC_NULL and
+ * every val_size[i] is 0.
+ *
+ * Every pointer is device memory, store_used (one u64) and status (one u32)
+ * included.  `work` is device scratch of lzf_gpu_set_store_work_size(count,
+ * in_bytes) bytes that must stay valid until the stream's work is done.
+ * Asynchronous on `stream`, with no host wait.  count: up to 2^32 - 1.
+ */
+#define LZF_STORE_OK     0
+#define LZF_STORE_FULL   1   /* base + packed bytes > store_cap */
+#define LZF_STORE_EWORK  2   /* in_bytes under-stated: the scratch slots do not fit in work */
+
+uint64_t lzf_gpu_set_store_work_size(uint32_t count, uint64_t in_bytes);
+int lzf_gpu_set_store(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len,
+                      uint32_t count, uint32_t max_in_len, uint64_t in_bytes, uint32_t compression,
+                      uint8_t *store, uint64_t store_cap, uint64_t *store_used,
+                      uint64_t *val_off, uint32_t *val_size, uint8_t *enc, uint32_t *status,
+                      void *work, void *stream);
+/* host, no HIP call: the STATS fold of src/query.c:400-405 over a batch's
+ * results (host copies of enc, val_size and in_len as val_len), once per
+ * value stored LZF, in index order -- what `count` gbSingleSet calls leave
+ * in server->stats.compravg, double for double */
+int lzf_host_store_stats(const uint8_t *enc, const uint32_t *val_size, const uint32_t *val_len,
+                         uint32_t count, double *compravg, uint64_t *ncompressed);
+
 /* Free the library's device scratch (all devices), the calling thread's and
  * the device workers' staging buffers; later calls allocate them again.
  * Each thread's staging buffers are also freed when the thread exits. */
