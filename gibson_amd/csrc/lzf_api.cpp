@@ -815,6 +815,69 @@ int lzf_gpu_set_store(const uint8_t *in, const uint64_t *in_off, const uint32_t 
     return e == hipSuccess ? LZF_GPU_OK : code_of(e);
 }
 
+int lzf_gpu_store_delete(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count, void *stream)
+{
+    if (!idx || !enc || !count) return LZF_GPU_EARG;
+    if (!n) return LZF_GPU_OK;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    const hipError_t e = lzf_launch_store_delete(idx, n, enc, count, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_gpu_store_expire(const int64_t *item_time, const int32_t *ttl, int64_t now,
+                         uint8_t *enc, uint32_t count, uint32_t *expired, void *stream)
+{
+    if (!item_time || !ttl || !enc || !expired || !count) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    const hipError_t e = lzf_launch_store_expire(item_time, ttl, now, enc, count, expired, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+uint64_t lzf_gpu_store_compact_work_size(uint32_t count)
+{
+    return lzf_compact_work_bytes(count);
+}
+
+int lzf_gpu_store_usage(const uint32_t *val_size, const uint8_t *enc, uint32_t count,
+                        uint64_t *report, void *work, void *stream)
+{
+    if (!val_size || !enc || !count || !report || !work) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfCompactArgs a{};
+    a.val_size = const_cast<uint32_t *>(val_size);         /* usage only reads */
+    a.enc = enc; a.count = count; a.report = report;
+    lzf_compact_carve(a, work);
+    const hipError_t e = lzf_launch_store_usage(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_gpu_store_compact(const uint8_t *src, uint64_t src_cap,
+                          uint64_t *val_off, uint32_t *val_size, const uint8_t *enc, uint32_t count,
+                          uint8_t *dst, uint64_t dst_cap, uint64_t *dst_used,
+                          uint64_t *report, uint32_t *status, void *work, void *stream)
+{
+    if (!src || !val_off || !val_size || !enc || !dst || !dst_used || !report || !status || !work)
+        return LZF_GPU_EARG;
+    if (!count || !src_cap || !dst_cap) return LZF_GPU_EARG;
+    /* a semispace copy: the arenas must not share a byte.  The ends saturate */
+    const uint64_t s0 = (uint64_t)(uintptr_t)src, d0 = (uint64_t)(uintptr_t)dst;
+    const uint64_t s1 = s0 + src_cap < s0 ? ~0ull : s0 + src_cap, d1 = d0 + dst_cap < d0 ? ~0ull : d0 + dst_cap;
+    if (d0 < s1 && s0 < d1) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfCompactArgs a{};
+    a.src = src; a.src_cap = src_cap;
+    a.val_off = val_off; a.val_size = val_size; a.enc = enc; a.count = count;
+    a.dst = dst; a.dst_cap = dst_cap; a.dst_used = dst_used;
+    a.report = report; a.status = status;
+    lzf_compact_carve(a, work);
+    const hipError_t e = lzf_launch_store_compact(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
 int lzf_gpu_selfcheck(void)
 {
     int rc = current_device_ok();

@@ -73,6 +73,26 @@ struct LzfStoreArgs {
     uint8_t *w_slots;
 };
 
+/* the store's lifecycle (lzf_store.hip): usage and the semispace compaction;
+ * device pointers.  Usage alone: val_off, src, dst, dst_used, status NULL */
+struct LzfCompactArgs {
+    const uint8_t *src;
+    uint64_t src_cap;
+    uint64_t *val_off;
+    uint32_t *val_size;
+    const uint8_t *enc;
+    uint32_t count;
+    uint8_t *dst;
+    uint64_t dst_cap;
+    uint64_t *dst_used;
+    uint64_t *report;
+    uint32_t *status;
+    /* work area (lzf_compact_carve): per scan tile the live count (top bit: a
+     * live item out of range), the live bytes and the dead bytes; the dense
+     * list of the live items, destination and source offset per live rank */
+    uint64_t *w_state, *w_tile_n, *w_tile_b, *w_tile_d, *w_live_dst, *w_live_src;
+};
+
 /* compress scratch of the lane generation (lzf_lane.hip), device pointers:
  * per value cstride u16 cand words and bstride u32 inserted-bitmap words */
 struct LzfLaneScratch {
@@ -138,6 +158,15 @@ hipError_t lzf_launch_store(LzfStoreArgs &a, hipStream_t s,
                             hipError_t (*compress)(const LzfBatch &, hipStream_t));
 uint64_t lzf_store_work_bytes(uint32_t count, uint64_t in_bytes);
 void lzf_store_carve(LzfStoreArgs &a, void *work);
+/* the store's lifecycle (lzf_store.hip): items nulled by index and by TTL,
+ * the usage report, and the compaction of the live items into a second arena */
+hipError_t lzf_launch_store_delete(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count, hipStream_t s);
+hipError_t lzf_launch_store_expire(const int64_t *item_time, const int32_t *ttl, int64_t now, uint8_t *enc,
+                                   uint32_t count, uint32_t *expired, hipStream_t s);
+hipError_t lzf_launch_store_usage(LzfCompactArgs &a, hipStream_t s);
+hipError_t lzf_launch_store_compact(LzfCompactArgs &a, hipStream_t s);
+uint64_t lzf_compact_work_bytes(uint32_t count);
+void lzf_compact_carve(LzfCompactArgs &a, void *work);
 /* value moves between mapped host memory and device arenas (lzf_hostio.hip):
  * len[k] (at least min_len) bytes from src + src_off[k] to dst + dst_off[k] */
 hipError_t lzf_launch_move(const uint8_t *src, const uint64_t *src_off, uint8_t *dst, const uint64_t *dst_off,

@@ -46,6 +46,11 @@
  * byte into one aligned 16-byte store, one lane per granule, after the tile's
  * whole granules.
  *
+ * The store's lifecycle (lzf_gpu_store_delete / _expire / _usage / _compact)
+ * is further down: items are marked dead in enc, and the live ones are packed
+ * into a second arena by the same scans and the same pack kernel, which is a
+ * template over where its offset table and its sources come from.
+ *
  * The kernels are helpers of this translation unit, not part of the library's
  * routed kernel set: they have internal linkage (anonymous namespace).
  */
@@ -294,35 +299,55 @@ __device__ inline const uint8_t *st_source_ptr(const LzfStoreArgs &a, uint64_t f
     return (from & ST_FROM_SLOT ? a.w_slots : a.in) + (from & ~ST_FROM_SLOT);
 }
 
-/* The value that holds byte p of the store (an offset from the store's start),
- * for the values [i0, i1) of one tile: its first byte vo, its end ve -- the
- * next value's offset, the packing is dense -- and its source.  From the
+/* What the pack kernel packs, the one thing its two callers differ in: a
+ * table of `entries()` destination offsets (monotone, ties at entries without
+ * bytes; entries() may be known on the device only), the source of entry i as
+ * one word and the address that word names, the destination arena, and the
+ * packed range [base(), base() + total()).  set_store: one entry per value of
+ * the batch, the sources in the input arena or the compress slots */
+struct StPackSet {
+    LzfStoreArgs a;
+    __device__ inline const uint64_t *off() const { return a.val_off; }
+    __device__ inline uint32_t entries() const { return a.count; }
+    __device__ inline uint64_t source(uint32_t i) const { return st_source(a, i); }
+    __device__ inline const uint8_t *source_ptr(uint64_t from) const { return st_source_ptr(a, from); }
+    __device__ inline uint8_t *store() const { return a.store; }
+    __device__ inline uint64_t base() const { return a.w_state[ST_BASE]; }
+    __device__ inline uint64_t total() const { return a.w_state[ST_TOTAL]; }
+};
+
+/* The entry that holds byte p of the store (an offset from the store's start),
+ * for the entries [i0, i1) of one tile: its first byte vo, its end ve -- the
+ * next entry's offset, the packing is dense -- and its source.  From the
  * arrays in HBM: */
+template <typename P>
 struct StMapGlobal {
-    const LzfStoreArgs &a;
-    uint32_t i0, i1;
+    const P &p;
+    const uint64_t *off;
+    uint32_t i0, i1, n;
     uint64_t end;                      /* base + total */
-    __device__ inline void at(uint64_t p, uint64_t &vo, uint64_t &ve, const uint8_t *&src) const
+    __device__ inline void at(uint64_t b, uint64_t &vo, uint64_t &ve, const uint8_t *&src) const
     {
-        const uint32_t i = st_find(a.val_off, i0, i1, p);
-        vo = a.val_off[i];
-        ve = i + 1u < a.count ? a.val_off[i + 1u] : end;
-        src = st_source_ptr(a, st_source(a, i));
+        const uint32_t i = st_find(off, i0, i1, b);
+        vo = off[i];
+        ve = i + 1u < n ? off[i + 1u] : end;
+        src = p.source_ptr(p.source(i));
     }
 };
 
 /* ... and from the tile's copy of them in LDS (off: n + 1 entries), which
  * takes the dependent loads from HBM out of every granule's way */
+template <typename P>
 struct StMapLds {
-    const LzfStoreArgs &a;
+    const P &p;
     const uint64_t *off, *from;
     uint32_t n;
-    __device__ inline void at(uint64_t p, uint64_t &vo, uint64_t &ve, const uint8_t *&src) const
+    __device__ inline void at(uint64_t b, uint64_t &vo, uint64_t &ve, const uint8_t *&src) const
     {
-        const uint32_t k = st_find(off, 0u, n, p);
+        const uint32_t k = st_find(off, 0u, n, b);
         vo = off[k];
         ve = off[k + 1u];
-        src = st_source_ptr(a, from[k]);
+        src = p.source_ptr(from[k]);
     }
 };
 
@@ -332,8 +357,7 @@ struct StMapLds {
  * flight at once, then one aligned 16-byte store (byte stores for a partial
  * granule).  Absolute addresses; sa: the store's address */
 template <typename Map>
-__device__ inline void st_pack_edge(const LzfStoreArgs &a, const Map &m, uint64_t sa, uint64_t g, uint64_t lo,
-                                    uint64_t hi)
+__device__ inline void st_pack_edge(uint8_t *store, const Map &m, uint64_t sa, uint64_t g, uint64_t lo, uint64_t hi)
 {
     const uint64_t q0 = g > lo ? g : lo, q1 = g + 16u < hi ? g + 16u : hi;
     uint64_t vo = 0ull, ve = 0ull;
@@ -347,12 +371,12 @@ __device__ inline void st_pack_edge(const LzfStoreArgs &a, const Map &m, uint64_
         w[j >> 2] |= (uint32_t)src[p - vo] << (8u * (j & 3u));
     }
     if (q1 - q0 == 16u) {
-        *(uint4 *)(a.store + (g - sa)) = make_uint4(w[0], w[1], w[2], w[3]);
+        *(uint4 *)(store + (g - sa)) = make_uint4(w[0], w[1], w[2], w[3]);
         return;
     }
 #pragma unroll
     for (uint32_t j = 0; j < 16u; j++)
-        if (g + j >= q0 && g + j < q1) a.store[g + j - sa] = (uint8_t)(w[j >> 2] >> (8u * (j & 3u)));
+        if (g + j >= q0 && g + j < q1) store[g + j - sa] = (uint8_t)(w[j >> 2] >> (8u * (j & 3u)));
 }
 
 /* one tile: bytes [lo, hi), absolute addresses like the tile's 16-byte
@@ -361,8 +385,7 @@ __device__ inline void st_pack_edge(const LzfStoreArgs &a, const Map &m, uint64_
  * aligned 16-byte store.  The other granules: in place (EDGES), or left to
  * the caller */
 template <bool REALIGN, bool EDGES, typename Map>
-__device__ inline void st_pack_tile(const LzfStoreArgs &a, const Map &m, uint64_t sa, uint64_t ta, uint64_t lo,
-                                    uint64_t hi)
+__device__ inline void st_pack_tile(uint8_t *store, const Map &m, uint64_t sa, uint64_t ta, uint64_t lo, uint64_t hi)
 {
     for (uint64_t gb = ta + 16ull * threadIdx.x; gb < hi; gb += 64ull * ST_BLOCK) {
         uint4 v[4];
@@ -388,11 +411,11 @@ __device__ inline void st_pack_tile(const LzfStoreArgs &a, const Map &m, uint64_
         }
 #pragma unroll
         for (uint32_t u = 0; u < 4u; u++)
-            if (how[u] == 1u) *(uint4 *)(a.store + (gb + 16ull * ST_BLOCK * u - sa)) = v[u];
+            if (how[u] == 1u) *(uint4 *)(store + (gb + 16ull * ST_BLOCK * u - sa)) = v[u];
         if (EDGES) {
 #pragma unroll
             for (uint32_t u = 0; u < 4u; u++)
-                if (how[u] == 2u) st_pack_edge(a, m, sa, gb + 16ull * ST_BLOCK * u, lo, hi);
+                if (how[u] == 2u) st_pack_edge(store, m, sa, gb + 16ull * ST_BLOCK * u, lo, hi);
         }
     }
 }
@@ -401,24 +424,26 @@ __device__ inline void st_pack_tile(const LzfStoreArgs &a, const Map &m, uint64_
  * them up in HBM */
 #define ST_LDS_VALS 512u
 
-template <bool REALIGN>
-__global__ __launch_bounds__(ST_BLOCK) void lzf_store_pack_kernel(LzfStoreArgs a, uint32_t tile)
+template <bool REALIGN, typename P>
+__global__ __launch_bounds__(ST_BLOCK) void lzf_store_pack_kernel(P p, uint32_t tile)
 {
     __shared__ uint64_t s_off[ST_LDS_VALS + 1u], s_from[ST_LDS_VALS];
     __shared__ uint32_t sc[ST_WAVES];
-    const uint64_t total = a.w_state[ST_TOTAL];
+    const uint64_t total = p.total();
     if (!total) return;                                   /* refused, or nothing to store */
     /* absolute addresses: the packed range [d0, d1), tiles from a0 (which may
      * lie up to 15 bytes before d0: nothing is accessed there) */
-    const uint64_t sa = (uint64_t)(uintptr_t)a.store, d0 = sa + a.w_state[ST_BASE], d1 = d0 + total;
+    uint8_t *const store = p.store();
+    const uint64_t sa = (uint64_t)(uintptr_t)store, d0 = sa + p.base(), d1 = d0 + total;
     const uint64_t a0 = d0 & ~15ull;
     const uint64_t ntile = (d1 - a0 + tile - 1u) / tile;
-    const uint64_t *__restrict__ voff = a.val_off;
+    const uint64_t *__restrict__ voff = p.off();
+    const uint32_t count = p.entries();
     for (uint64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
         const uint64_t ta = a0 + t * tile;
         const uint64_t lo = ta > d0 ? ta : d0, hi = ta + tile < d1 ? ta + tile : d1;
         /* i0: the value that holds byte lo */
-        const uint32_t i0 = st_find_block(voff, 0u, a.count, lo - sa, sc);
+        const uint32_t i0 = st_find_block(voff, 0u, count, lo - sa, sc);
         __syncthreads();                                  /* the tile before is done with the table */
         /* the ST_LDS_VALS + 1 entries from i0 into LDS, and n: how many of
          * them start at or before the tile's last byte -- the tile's values
@@ -426,20 +451,20 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_store_pack_kernel(LzfStoreArgs a
         uint32_t yes = 0u;
         for (uint32_t k = threadIdx.x; k < ST_LDS_VALS + ST_BLOCK; k += ST_BLOCK) {
             const uint64_t i = (uint64_t)i0 + k;
-            const bool in = k <= ST_LDS_VALS && i < a.count;
+            const bool in = k <= ST_LDS_VALS && i < count;
             const uint64_t o = in ? voff[i] : d1 - sa;
             if (k <= ST_LDS_VALS) s_off[k] = o;
-            if (in && k < ST_LDS_VALS) s_from[k] = st_source(a, (uint32_t)i);
+            if (in && k < ST_LDS_VALS) s_from[k] = p.source((uint32_t)i);
             yes += (uint32_t)__popcll(__ballot(in && o <= hi - 1u - sa));
         }
         const uint32_t n = st_block_count(yes, sc);       /* its barrier: the table is written */
         if (n > ST_LDS_VALS) {                            /* a run of tiny values: look them up in HBM */
-            const uint32_t i1 = st_find_block(voff, i0, a.count, hi - 1u - sa, sc) + 1u;
-            st_pack_tile<REALIGN, true>(a, StMapGlobal{a, i0, i1, d1 - sa}, sa, ta, lo, hi);
+            const uint32_t i1 = st_find_block(voff, i0, count, hi - 1u - sa, sc) + 1u;
+            st_pack_tile<REALIGN, true>(store, StMapGlobal<P>{p, voff, i0, i1, count, d1 - sa}, sa, ta, lo, hi);
             continue;
         }
-        const StMapLds m{a, s_off, s_from, n};
-        st_pack_tile<REALIGN, false>(a, m, sa, ta, lo, hi);
+        const StMapLds<P> m{p, s_off, s_from, n};
+        st_pack_tile<REALIGN, false>(store, m, sa, ta, lo, hi);
         /* the granules not inside one value are those that hold a cut -- a
          * value's start, or the range's end -- at an address that is no
          * multiple of 16: one lane per cut, so a wave works on 64 of them at
@@ -453,9 +478,201 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_store_pack_kernel(LzfStoreArgs a
                 const uint64_t pc = sa + s_off[k - 1u];
                 if ((pc & 15ull) && (pc & ~15ull) == g && pc >= lo) continue;
             }
-            st_pack_edge(a, m, sa, g, lo, hi);
+            st_pack_edge(store, m, sa, g, lo, hi);
         }
     }
+}
+
+/* ---- the store's lifecycle: delete, expire, usage, compact ------------------
+ *
+ * An item is dead once enc[i] == LZF_ENC_NULL.  Compaction is a semispace
+ * copy: the same reduce / carry / write scan as above, over two sums per item
+ * (live items and live bytes), decides the whole call in the carry kernel,
+ * and the write pass -- only when the call was accepted -- emits the dense
+ * list of the live items (destination offset, source offset, one entry per
+ * live rank) that the pack kernel then runs over: a tile's table holds live
+ * items only, however many dead ones lie between them. */
+
+enum { ST_NLIVE = 4 };
+
+/* both sums of one item in one word, for the scan inside a tile: a tile's
+ * live bytes stay below 2^42 (1024 items of less than 2^32 bytes), its live
+ * count (at most 1024) rides from bit 48 up */
+#define ST_LIVE_ONE   (1ull << 48)
+#define ST_LIVE_BYTES (ST_LIVE_ONE - 1ull)
+/* w_tile_n, between reduce and carry: a live item of the tile is out of range */
+#define ST_TILE_BAD   (1ull << 63)
+
+/* RANGE: also fold whether a live item's [val_off, val_off + val_size) leaves
+ * [0, src_cap) (usage has no offsets to check) */
+template <bool RANGE>
+__global__ __launch_bounds__(ST_BLOCK) void lzf_compact_reduce_kernel(LzfCompactArgs a)
+{
+    __shared__ uint64_t sw[ST_WAVES];
+    const uint64_t first = (uint64_t)blockIdx.x * ST_TILE + threadIdx.x * ST_PER;
+    uint64_t s = 0ull, dead = 0ull;
+    int bad = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < ST_PER; k++) {
+        const uint64_t i = first + k;
+        if (i >= a.count) break;
+        const uint64_t size = a.val_size[i];
+        if (a.enc[i] == (uint8_t)LZF_ENC_NULL) {
+            dead += size;
+            continue;
+        }
+        s += ST_LIVE_ONE + size;
+        if (RANGE) {
+            const uint64_t off = a.val_off[i];
+            bad |= off > a.src_cap || size > a.src_cap - off;
+        }
+    }
+    uint64_t tot, dtot;
+    (void)st_block_excl(s, sw, &tot);
+    (void)st_block_excl(dead, sw, &dtot);
+    if (RANGE) bad = __syncthreads_or(bad);
+    if (threadIdx.x != 0u) return;
+    a.w_tile_n[blockIdx.x] = (tot >> 48) | (bad ? ST_TILE_BAD : 0ull);
+    a.w_tile_b[blockIdx.x] = tot & ST_LIVE_BYTES;
+    a.w_tile_d[blockIdx.x] = dtot;
+}
+
+/* one workgroup: the totals for the report and, COMPACT, the exclusive scans
+ * of the tiles' live counts and live bytes in place and the whole-call
+ * decision */
+template <bool COMPACT>
+__global__ __launch_bounds__(ST_BLOCK) void lzf_compact_carry_kernel(LzfCompactArgs a, uint32_t ntile)
+{
+    __shared__ uint64_t sw[ST_WAVES];
+    uint64_t rn = 0ull, rb = 0ull, rd = 0ull;
+    int bad = 0;
+    for (uint32_t c = 0; c < ntile; c += ST_BLOCK) {
+        const uint32_t i = c + threadIdx.x;
+        uint64_t xn = i < ntile ? a.w_tile_n[i] : 0ull;
+        const uint64_t xb = i < ntile ? a.w_tile_b[i] : 0ull, xd = i < ntile ? a.w_tile_d[i] : 0ull;
+        bad |= (int)(xn >> 63);
+        xn &= ~ST_TILE_BAD;
+        uint64_t tn, tb, td;
+        const uint64_t on = st_block_excl(xn, sw, &tn), ob = st_block_excl(xb, sw, &tb);
+        (void)st_block_excl(xd, sw, &td);
+        if (COMPACT && i < ntile) {
+            a.w_tile_n[i] = rn + on;
+            a.w_tile_b[i] = rb + ob;
+        }
+        rn += tn;
+        rb += tb;
+        rd += td;
+    }
+    if (COMPACT) bad = __syncthreads_or(bad);
+    if (threadIdx.x != 0u) return;
+    a.report[0] = rn;
+    a.report[1] = rb;
+    a.report[2] = (uint64_t)a.count - rn;
+    a.report[3] = rd;
+    if (!COMPACT) return;
+    const uint64_t base = *a.dst_used, end = base + rb;
+    uint32_t st = LZF_STORE_OK;
+    if (bad) st = LZF_STORE_ERANGE;
+    else if (end < base || end > a.dst_cap) st = LZF_STORE_FULL;
+    a.w_state[ST_BASE] = base;
+    a.w_state[ST_TOTAL] = st == LZF_STORE_OK ? rb : 0ull;
+    a.w_state[ST_STATUS] = st;
+    a.w_state[ST_NLIVE] = st == LZF_STORE_OK ? rn : 0ull;
+    *a.status = st;
+    if (st == LZF_STORE_OK) *a.dst_used = end;
+}
+
+/* an accepted call only: the live list, then every item's new offset and a
+ * dead item's size 0.  An item's old offset is read by the thread that
+ * replaces it, and the pack kernel reads the list, not val_off */
+__global__ __launch_bounds__(ST_BLOCK) void lzf_compact_write_kernel(LzfCompactArgs a)
+{
+    __shared__ uint64_t sw[ST_WAVES];
+    if (a.w_state[ST_STATUS] != 0ull) return;             /* refused: the arrays stay as they are */
+    const uint64_t first = (uint64_t)blockIdx.x * ST_TILE + threadIdx.x * ST_PER;
+    uint64_t v[ST_PER], s = 0ull;
+#pragma unroll
+    for (uint32_t k = 0; k < ST_PER; k++) {
+        const uint64_t i = first + k;
+        v[k] = i < a.count && a.enc[i] != (uint8_t)LZF_ENC_NULL ? ST_LIVE_ONE + a.val_size[i] : 0ull;
+        s += v[k];
+    }
+    uint64_t tot;
+    const uint64_t o = st_block_excl(s, sw, &tot);
+    uint64_t rank = a.w_tile_n[blockIdx.x] + (o >> 48);
+    uint64_t off = a.w_state[ST_BASE] + a.w_tile_b[blockIdx.x] + (o & ST_LIVE_BYTES);
+#pragma unroll
+    for (uint32_t k = 0; k < ST_PER; k++) {
+        const uint64_t i = first + k;
+        if (i >= a.count) break;
+        if (v[k]) {
+            a.w_live_dst[rank] = off;
+            a.w_live_src[rank] = a.val_off[i];
+            rank++;
+        } else {
+            a.val_size[i] = 0u;
+        }
+        a.val_off[i] = off;
+        off += v[k] & ST_LIVE_BYTES;
+    }
+}
+
+/* compaction's plan for the pack kernel: one entry per live item, the source
+ * an offset into the old arena.  A realigning load reads the aligned 16 bytes
+ * around a value's last byte, which lie in that byte's page */
+struct StPackLive {
+    LzfCompactArgs a;
+    __device__ inline const uint64_t *off() const { return a.w_live_dst; }
+    __device__ inline uint32_t entries() const { return (uint32_t)a.w_state[ST_NLIVE]; }
+    __device__ inline uint64_t source(uint32_t i) const { return a.w_live_src[i]; }
+    __device__ inline const uint8_t *source_ptr(uint64_t from) const { return a.src + from; }
+    __device__ inline uint8_t *store() const { return a.dst; }
+    __device__ inline uint64_t base() const { return a.w_state[ST_BASE]; }
+    __device__ inline uint64_t total() const { return a.w_state[ST_TOTAL]; }
+};
+
+#define ST_SWEEP_GRID 2048u               /* grid-stride kernels: 256 CUs x 8 workgroups */
+
+/* DEL / overwrite by index.  Byte stores: indices that share a 4-byte word of
+ * enc, or repeat, all store the same byte and none reads */
+__global__ __launch_bounds__(ST_BLOCK) void lzf_store_delete_kernel(const uint32_t *__restrict__ idx, uint32_t n,
+                                                                    uint8_t *enc, uint32_t count)
+{
+    const uint64_t step = (uint64_t)gridDim.x * ST_BLOCK;
+    for (uint64_t k = (uint64_t)blockIdx.x * ST_BLOCK + threadIdx.x; k < n; k += step) {
+        const uint32_t i = idx[k];
+        if (i < count) enc[i] = (uint8_t)LZF_ENC_NULL;
+    }
+}
+
+/* the TTL rule of src/query.c:186-189 over every item that is not NULL yet;
+ * the count by wave ballot, one atomic add per wave.  Every lane of a
+ * workgroup makes the same number of rounds */
+__global__ __launch_bounds__(ST_BLOCK) void lzf_store_expire_kernel(const int64_t *__restrict__ item_time,
+                                                                    const int32_t *__restrict__ ttl, int64_t now,
+                                                                    uint8_t *enc, uint32_t count, uint32_t *expired)
+{
+    const uint64_t step = (uint64_t)gridDim.x * ST_BLOCK;
+    uint32_t hits = 0u;
+    for (uint64_t b = (uint64_t)blockIdx.x * ST_BLOCK; b < count; b += step) {
+        const uint64_t i = b + threadIdx.x;
+        bool hit = false;
+        if (i < count && enc[i] != (uint8_t)LZF_ENC_NULL) {
+            const int32_t t = ttl[i];
+            /* now - time in two's complement, as the reference's time_t arithmetic wraps */
+            const int64_t age = (int64_t)((uint64_t)now - (uint64_t)item_time[i]);
+            hit = t > 0 && age >= (int64_t)t;
+            if (hit) enc[i] = (uint8_t)LZF_ENC_NULL;
+        }
+        hits += (uint32_t)__popcll(__ballot(hit));
+    }
+    if ((threadIdx.x & 63u) == 0u && hits) atomicAdd(expired, hits);
+}
+
+static inline uint32_t st_sweep_grid(uint64_t n)
+{
+    const uint64_t g = (n + ST_BLOCK - 1u) / ST_BLOCK;
+    return (uint32_t)(g < ST_SWEEP_GRID ? g : ST_SWEEP_GRID);
 }
 
 /* LZF_GPU_STORE_TILE_KB (diagnostics, read per launch): the pack tile in KiB,
@@ -476,6 +693,21 @@ bool st_pack_realign()
 {
     const char *e = getenv("LZF_GPU_STORE_PACK");
     return e && !strcmp(e, "realign");
+}
+
+/* the pack launch: the grid from the host's bound on the packed bytes; the
+ * kernel strides over the tiles there really are */
+template <typename P>
+hipError_t st_launch_pack(const P &p, uint64_t most_bytes, hipStream_t s)
+{
+    const uint32_t tile = st_pack_tile();
+    const uint64_t most = most_bytes / tile + 2u;
+    const uint32_t grid = (uint32_t)(most < ST_PACK_GRID ? most : ST_PACK_GRID);
+    if (st_pack_realign())
+        hipLaunchKernelGGL((lzf_store_pack_kernel<true, P>), dim3(grid), dim3(ST_BLOCK), 0, s, p, tile);
+    else
+        hipLaunchKernelGGL((lzf_store_pack_kernel<false, P>), dim3(grid), dim3(ST_BLOCK), 0, s, p, tile);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -520,14 +752,60 @@ hipError_t lzf_launch_store(LzfStoreArgs &a, hipStream_t s, hipError_t (*compres
     hipLaunchKernelGGL(lzf_store_carry_kernel<true>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
     hipLaunchKernelGGL(lzf_store_write_kernel<true>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    /* the grid from the host's bound on the packed bytes; the kernel strides
-     * over the tiles there really are */
-    const uint32_t tile = st_pack_tile();
-    const uint64_t most = st_slot_room(a.in_bytes, a.count) / tile + 2u;
-    const uint32_t grid = (uint32_t)(most < ST_PACK_GRID ? most : ST_PACK_GRID);
-    if (st_pack_realign())
-        hipLaunchKernelGGL(lzf_store_pack_kernel<true>, dim3(grid), dim3(ST_BLOCK), 0, s, a, tile);
-    else
-        hipLaunchKernelGGL(lzf_store_pack_kernel<false>, dim3(grid), dim3(ST_BLOCK), 0, s, a, tile);
+    return st_launch_pack(StPackSet{a}, st_slot_room(a.in_bytes, a.count), s);
+}
+
+uint64_t lzf_compact_work_bytes(uint32_t count)
+{
+    /* state (8 x u64) | three tile sums (u64 per tile) | the live list (2 x
+     * u64 per item); room to align the caller's pointer.  Below 2^37 */
+    return 64u + (uint64_t)st_tiles(count) * 24u + (uint64_t)count * 16u + 16u;
+}
+
+void lzf_compact_carve(LzfCompactArgs &a, void *work)
+{
+    uint8_t *w = (uint8_t *)(((uintptr_t)work + 15u) & ~(uintptr_t)15u);
+    const size_t nt = st_tiles(a.count);
+    a.w_state = (uint64_t *)w;            w += 64;
+    a.w_tile_n = (uint64_t *)w;           w += nt * 8;
+    a.w_tile_b = (uint64_t *)w;           w += nt * 8;
+    a.w_tile_d = (uint64_t *)w;           w += nt * 8;
+    a.w_live_dst = (uint64_t *)w;         w += (size_t)a.count * 8;
+    a.w_live_src = (uint64_t *)w;
+}
+
+hipError_t lzf_launch_store_delete(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count, hipStream_t s)
+{
+    hipLaunchKernelGGL(lzf_store_delete_kernel, dim3(st_sweep_grid(n)), dim3(ST_BLOCK), 0, s, idx, n, enc, count);
     return hipGetLastError();
+}
+
+hipError_t lzf_launch_store_expire(const int64_t *item_time, const int32_t *ttl, int64_t now, uint8_t *enc,
+                                   uint32_t count, uint32_t *expired, hipStream_t s)
+{
+    const hipError_t e = hipMemsetAsync(expired, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lzf_store_expire_kernel, dim3(st_sweep_grid(count)), dim3(ST_BLOCK), 0, s, item_time, ttl, now,
+                       enc, count, expired);
+    return hipGetLastError();
+}
+
+hipError_t lzf_launch_store_usage(LzfCompactArgs &a, hipStream_t s)
+{
+    const uint32_t nt = st_tiles(a.count);
+    hipLaunchKernelGGL(lzf_compact_reduce_kernel<false>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_compact_carry_kernel<false>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
+    return hipGetLastError();
+}
+
+hipError_t lzf_launch_store_compact(LzfCompactArgs &a, hipStream_t s)
+{
+    const uint32_t nt = st_tiles(a.count);
+    hipLaunchKernelGGL(lzf_compact_reduce_kernel<true>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_compact_carry_kernel<true>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_compact_write_kernel, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    /* the live bytes fit in both arenas, or the call is refused */
+    return st_launch_pack(StPackLive{a}, a.dst_cap < a.src_cap ? a.dst_cap : a.src_cap, s);
 }

@@ -52,6 +52,11 @@ EXPORTS = (
     "lzf_gpu_set_store_work_size",
     "lzf_gpu_set_store",
     "lzf_host_store_stats",
+    "lzf_gpu_store_delete",
+    "lzf_gpu_store_expire",
+    "lzf_gpu_store_usage",
+    "lzf_gpu_store_compact_work_size",
+    "lzf_gpu_store_compact",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -60,6 +65,8 @@ KIND_COMPRESS, KIND_DECOMPRESS = 0, 1
 
 # *status of set_store (include/lzf_gpu.h)
 STORE_OK, STORE_FULL, STORE_EWORK = 0, 1, 2
+# *status of store_compact only: a live item's bytes leave the source arena
+STORE_ERANGE = 3
 
 # item encodings (src/net.h:274-278) and the MGET reply code (src/query.h:71)
 ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
@@ -167,6 +174,8 @@ def _load(path):
         _bind_mixed(L)
     if hasattr(L, "lzf_gpu_set_store"):
         _bind_store(L)
+    if hasattr(L, "lzf_gpu_store_compact"):
+        _bind_store_lifecycle(L)
     del i32
     _LOADED[path] = L
     return L
@@ -209,6 +218,23 @@ def _bind_store(L):
     L.lzf_gpu_set_store.argtypes = [vp, vp, vp, u32, u32, u64, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]
     L.lzf_host_store_stats.restype = ctypes.c_int
     L.lzf_host_store_stats.argtypes = [vp, vp, vp, u32, vp, vp]
+
+
+def _bind_store_lifecycle(L):
+    """Delete, expire, usage and compact of the device store; absent from an
+    older build given by LZF_HIP_LIB (the helpers below then raise
+    AttributeError)."""
+    u32, u64, vp, i64 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64
+    L.lzf_gpu_store_delete.restype = ctypes.c_int
+    L.lzf_gpu_store_delete.argtypes = [vp, u32, vp, u32, vp]
+    L.lzf_gpu_store_expire.restype = ctypes.c_int
+    L.lzf_gpu_store_expire.argtypes = [vp, vp, i64, vp, u32, vp, vp]
+    L.lzf_gpu_store_usage.restype = ctypes.c_int
+    L.lzf_gpu_store_usage.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.lzf_gpu_store_compact_work_size.restype = u64
+    L.lzf_gpu_store_compact_work_size.argtypes = [u32]
+    L.lzf_gpu_store_compact.restype = ctypes.c_int
+    L.lzf_gpu_store_compact.argtypes = [vp, u64, vp, vp, vp, u32, vp, u64, vp, vp, vp, vp, vp]
 
 
 def selfcheck():
@@ -472,6 +498,63 @@ def store_stats(enc, val_size, val_len, compravg=0.0, ncompressed=0):
     _check(lib().lzf_host_store_stats(_np_ptr(e), _np_ptr(s), _np_ptr(v), len(e), ctypes.byref(avg),
                                       ctypes.byref(n)), "lzf_host_store_stats")
     return avg.value, n.value
+
+
+# ---- the device store's lifecycle --------------------------------------------
+
+def store_delete(idx, enc, stream=None):
+    """DEL / overwrite by index: enc[idx[k]] = ENC_NULL.  idx int32 (read as
+    u32), enc uint8, on one device; an index past enc's length is ignored and
+    duplicates are fine.  No host wait."""
+    _check(lib().lzf_gpu_store_delete(_ptr(idx), int(idx.numel()), _ptr(enc), int(enc.numel()),
+                                      _stream_handle(stream)), "lzf_gpu_store_delete")
+
+
+def store_expire(item_time, ttl, now, enc, expired, stream=None):
+    """TTL sweep (src/query.c:186-189): item i becomes ENC_NULL iff ttl[i] > 0
+    and now - item_time[i] >= ttl[i].  item_time int64, ttl int32, enc uint8,
+    expired (1 element, int32) receives how many items this call nulled.  No
+    host wait."""
+    _check(lib().lzf_gpu_store_expire(_ptr(item_time), _ptr(ttl), int(now), _ptr(enc), int(enc.numel()),
+                                      _ptr(expired), _stream_handle(stream)), "lzf_gpu_store_expire")
+
+
+def store_compact_work(count, device):
+    """A scratch tensor for one store_usage or store_compact call over
+    ``count`` items."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_compact_work_size(int(count))), dtype=torch.uint8, device=device)
+
+
+def store_usage(val_size, enc, report, work=None, stream=None):
+    """report (4 elements, int64) = live items, their bytes, dead items, the
+    bytes the dead items' sizes still name.  No host wait; returns ``work``,
+    which must outlive the stream's work."""
+    n = enc.numel()
+    if work is None:
+        work = store_compact_work(n, enc.device)
+    _check(lib().lzf_gpu_store_usage(_ptr(val_size), _ptr(enc), n, _ptr(report), _ptr(work),
+                                     _stream_handle(stream)), "lzf_gpu_store_usage")
+    return work
+
+
+def store_compact(src, val_off, val_size, enc, dst, dst_used, report, status, work=None, stream=None):
+    """Semispace compaction: the stored bytes of every item with enc !=
+    ENC_NULL copied from ``src`` and packed densely in index order into
+    ``dst`` from ``dst_used[0]`` on, which is advanced; val_off / val_size
+    rewritten for ``dst`` (a dead item: size 0).  The caps are the tensors'
+    lengths.  status (1 element, int32): STORE_OK, or STORE_FULL /
+    STORE_ERANGE with the call refused whole and nothing changed; report as
+    store_usage fills it, either way.  No host wait; returns ``work``
+    (store_compact_work), which must outlive the stream's work."""
+    n = enc.numel()
+    if work is None:
+        work = store_compact_work(n, src.device)
+    rc = lib().lzf_gpu_store_compact(_ptr(src), int(src.numel()), _ptr(val_off), _ptr(val_size), _ptr(enc), n,
+                                     _ptr(dst), int(dst.numel()), _ptr(dst_used), _ptr(report), _ptr(status),
+                                     _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_compact")
+    return work
 
 
 def host_register(arr):

@@ -350,6 +350,79 @@ int lzf_gpu_set_store(const uint8_t *in, const uint64_t *in_off, const uint32_t 
 int lzf_host_store_stats(const uint8_t *enc, const uint32_t *val_size, const uint32_t *val_len,
                          uint32_t count, double *compravg, uint64_t *ncompressed);
 
+/*
+ * The device store's lifecycle: delete, TTL expiry, usage, compaction.
+ *
+ * The store is the three arrays lzf_gpu_set_store writes and lzf_gpu_kv_frame
+ * reads -- val_off[count] (u64), val_size[count] (u32), enc[count] (u8) --
+ * over an arena.  An item is dead once enc[i] == LZF_ENC_NULL; every other
+ * item is live (PLAIN, LZF, and NUMBER with its 8 stored bytes).  Item indices
+ * are stable: nothing here renumbers items, so a host-side key -> index map
+ * stays valid across a compaction.  Every pointer is device memory; every call
+ * validates its arguments before any HIP call, is asynchronous on `stream`
+ * and waits for nothing on the host, so SET, MGET, DEL / expire, compact and
+ * SET again queue behind each other on one stream.
+ */
+
+/* DEL / overwrite: enc[idx[k]] = LZF_ENC_NULL for k < n.  An index >= count is
+ * ignored; duplicates are fine; n == 0 does nothing.  val_off / val_size are
+ * left as they are (usage and compact read them). */
+int lzf_gpu_store_delete(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count, void *stream);
+
+/* TTL sweep, the rule of gbIsNodeStillValid / gbIsItemStillValid
+ * (src/query.c:186-189): item i expires iff ttl[i] > 0 and
+ * now - item_time[i] >= ttl[i]; then enc[i] = LZF_ENC_NULL.  Items already
+ * NULL are not counted.  *expired (one device u32) receives how many items
+ * this call nulled. */
+int lzf_gpu_store_expire(const int64_t *item_time, const int32_t *ttl, int64_t now,
+                         uint8_t *enc, uint32_t count, uint32_t *expired, void *stream);
+
+/* What a compaction would find, without moving anything: report[0] live items
+ * (enc != LZF_ENC_NULL), [1] their bytes (the sum of val_size), [2] dead
+ * items, [3] the bytes the dead items' val_size still name (0 after a
+ * compaction, which sets a dead item's size to 0).  report: 4 device u64.
+ * work: lzf_gpu_store_compact_work_size(count) bytes of device scratch. */
+int lzf_gpu_store_usage(const uint32_t *val_size, const uint8_t *enc, uint32_t count,
+                        uint64_t *report, void *work, void *stream);
+
+/*
+ * Compaction: a semispace collection from the arena src (src_cap bytes) into
+ * a second arena dst (dst_cap bytes).  The stored bytes of every live item
+ * are copied from src + val_off[i] and packed densely IN ITEM-INDEX ORDER from
+ * base = *dst_used, whatever order the old offsets were in (after overwrites
+ * they are not monotone in the index; the result is).  On success, for every
+ * i, live or dead, val_off[i] = base + the sizes of the live items before i;
+ * val_size[i] is unchanged for a live item and 0 for a dead one; enc is not
+ * written; *dst_used = base + the live bytes; *status = LZF_STORE_OK.  These
+ * are the invariants lzf_gpu_set_store leaves (monotone offsets, ties at dead
+ * and zero-size items), so a later lzf_gpu_set_store appends to dst and
+ * lzf_gpu_kv_frame reads it unchanged.  src is never written: the caller
+ * swaps the arenas afterwards.
+ *
+ * The call is refused as a whole with LZF_STORE_ERANGE when a live item's
+ * [val_off, val_off + val_size) leaves [0, src_cap), and otherwise with
+ * LZF_STORE_FULL when base + the live bytes exceed dst_cap or wrap.  Then
+ * val_off, val_size and *dst_used are unchanged, no byte of dst is written
+ * and no byte of an out-of-range item is read.  report (4 device u64) is
+ * filled either way, as lzf_gpu_store_usage fills it, from the values before
+ * the call.
+ *
+ * LZF_GPU_EARG: a NULL pointer, count == 0, a zero cap, or [dst, dst + dst_cap)
+ * overlapping [src, src + src_cap).  Compaction in place is not provided: it
+ * would need workgroups to wait for one another, or a chunked bounce through
+ * scratch; what is provided is the copy into a second arena.  `work`:
+ * lzf_gpu_store_compact_work_size(count) bytes of device scratch that must
+ * stay valid until the stream's work is done.  count: up to 2^32 - 1; all
+ * byte arithmetic is 64-bit.
+ */
+#define LZF_STORE_ERANGE 3   /* a live item's [val_off, val_off + val_size) leaves [0, src_cap) */
+
+uint64_t lzf_gpu_store_compact_work_size(uint32_t count);
+int lzf_gpu_store_compact(const uint8_t *src, uint64_t src_cap,
+                          uint64_t *val_off, uint32_t *val_size, const uint8_t *enc, uint32_t count,
+                          uint8_t *dst, uint64_t dst_cap, uint64_t *dst_used,
+                          uint64_t *report, uint32_t *status, void *work, void *stream);
+
 /* Free the library's device scratch (all devices), the calling thread's and
  * the device workers' staging buffers; later calls allocate them again.
  * Each thread's staging buffers are also freed when the thread exits. */
