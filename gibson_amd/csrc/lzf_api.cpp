@@ -878,6 +878,88 @@ int lzf_gpu_store_compact(const uint8_t *src, uint64_t src_cap,
     return e == hipSuccess ? LZF_GPU_OK : code_of(e);
 }
 
+uint64_t lzf_gpu_store_select_work_size(uint32_t count)
+{
+    return lzf_select_work_bytes(count);
+}
+
+int lzf_gpu_store_select_prefix(const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                                const uint8_t *enc, uint32_t count,
+                                const uint8_t *prefix, uint32_t prefix_len,
+                                uint32_t *sel, uint32_t cap, uint32_t *result, void *work, void *stream)
+{
+    if (!keys || !key_off || !key_len || !enc || !prefix || !sel || !result || !work) return LZF_GPU_EARG;
+    if (!count || !prefix_len || !cap) return LZF_GPU_EARG;   /* the reference asserts len > 0 */
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfSelectArgs a{};
+    a.keys = keys; a.key_off = key_off; a.key_len = key_len; a.enc = enc; a.count = count;
+    a.prefix = prefix; a.prefix_len = prefix_len;
+    a.sel = sel; a.cap = cap; a.result = result;
+    lzf_select_carve(a, work);
+    const hipError_t e = lzf_launch_store_select(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+uint64_t lzf_gpu_store_mget_work_size(uint32_t n)
+{
+    return lzf_mget_work_bytes(n);
+}
+
+int lzf_gpu_store_mget(const uint32_t *idx, uint32_t n,
+                       const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                       const uint8_t *store, const uint64_t *val_off, const uint32_t *val_size,
+                       uint8_t *enc, const uint32_t *val_len, uint32_t count,
+                       const int64_t *item_time, const int32_t *item_ttl, int64_t now,
+                       int64_t *last_access, uint32_t max_val_len, int reply_header,
+                       uint8_t *frame, uint64_t max_response, uint64_t *frame_len,
+                       uint64_t *result, void *work, void *stream)
+{
+    if (!idx || !keys || !key_off || !key_len || !store || !val_off || !val_size || !enc || !val_len ||
+        !frame || !frame_len || !result || !work)
+        return LZF_GPU_EARG;
+    if (!n || !count || !item_time != !item_ttl) return LZF_GPU_EARG;
+    if (max_val_len > LZF_GPU_MAX_VALUE) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfMgetArgs a{};
+    a.idx = idx; a.n = n;
+    a.keys = keys; a.key_off = key_off; a.key_len = key_len;
+    a.store = store; a.val_off = val_off; a.val_size = val_size;
+    a.enc = enc; a.val_len = val_len; a.count = count;
+    a.item_time = item_time; a.item_ttl = item_ttl; a.now = now; a.last_access = last_access;
+    a.max_val_len = max_val_len ? max_val_len : 1u;
+    a.reply_header = reply_header;
+    a.frame = frame; a.max_response = max_response; a.frame_len = frame_len; a.result = result;
+    lzf_mget_carve(a, work);
+    const hipError_t e = lzf_launch_store_mget(a, (hipStream_t)stream, launch_decompress);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_gpu_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
+                        const int64_t *item_time, const int32_t *item_ttl, int64_t now,
+                        int64_t *last_access, uint64_t *result, void *stream)
+{
+    if (!idx || !enc || !result || !n || !count || !item_time != !item_ttl) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    const hipError_t e = lzf_launch_store_count(idx, n, enc, count, item_time, item_ttl, now, last_access, result,
+                                                (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *enc, uint32_t count,
+                       int64_t *item_time, int32_t *item_ttl, int64_t now,
+                       int64_t *last_access, uint64_t *result, void *stream)
+{
+    if (!idx || !enc || !item_time || !item_ttl || !result || !n || !count) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    const hipError_t e = lzf_launch_store_mttl(idx, n, ttl, enc, count, item_time, item_ttl, now, last_access, result,
+                                               (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
 int lzf_gpu_selfcheck(void)
 {
     int rc = current_device_ok();

@@ -1,7 +1,8 @@
 /*
  * lzf_dev.h -- device helpers shared by the compress kernels (lzf_cand.hip):
  * unaligned byte-window loads that never touch memory past a value's end,
- * and the reference's slot function.
+ * and the reference's slot function; and the block-wide scan of the store's
+ * kernels (lzf_store.hip, lzf_mget.hip).
  */
 #ifndef GIBSON_AMD_LZF_DEV_H
 #define GIBSON_AMD_LZF_DEV_H
@@ -133,6 +134,37 @@ __device__ __forceinline__ void dv_st_exact(uint8_t *p, uint4 v, uint32_t len)
         a >>= 16;
     }
     if (len & 1u) *p = (uint8_t)a;
+}
+
+__device__ inline uint64_t dv_shfl_up64(uint64_t x, int d)
+{
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, d, 64);
+    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), d, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+/* block-wide exclusive scan of one u64 per thread (the scans of lzf_store.hip
+ * and lzf_mget.hip), for a workgroup of WAVES waves: an inclusive wave scan,
+ * then the totals of the waves before this one; sw: WAVES words of LDS */
+template <uint32_t WAVES>
+__device__ inline uint64_t dv_block_excl(uint64_t x, uint64_t *sw, uint64_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t inc = x;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = dv_shfl_up64(inc, d);
+        if (lane >= (uint32_t)d) inc += o;
+    }
+    if (lane == 63u) sw[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0ull, all = 0ull;
+    for (uint32_t w = 0; w < WAVES; w++) {
+        if (w < wave) before += sw[w];
+        all += sw[w];
+    }
+    __syncthreads();
+    *total = all;
+    return before + inc - x;
 }
 
 #endif

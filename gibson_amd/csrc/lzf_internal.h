@@ -93,6 +93,55 @@ struct LzfCompactArgs {
     uint64_t *w_state, *w_tile_n, *w_tile_b, *w_tile_d, *w_live_dst, *w_live_src;
 };
 
+/* the prefix select over the store's keys (lzf_mget.hip); device pointers */
+struct LzfSelectArgs {
+    const uint8_t *keys;
+    const uint64_t *key_off;
+    const uint32_t *key_len;
+    const uint8_t *enc;
+    uint32_t count;
+    const uint8_t *prefix;
+    uint32_t prefix_len;
+    uint32_t *sel;
+    uint32_t cap;
+    uint32_t *result;
+    /* work area (lzf_select_carve): one 64-bit match word per 64 items, and
+     * per tile its match count, then the matches before it */
+    uint64_t *w_mask, *w_tile;
+};
+
+/* MGET over an index list (lzf_mget.hip); device pointers */
+struct LzfMgetArgs {
+    const uint32_t *idx;
+    uint32_t n;
+    const uint8_t *keys;
+    const uint64_t *key_off;
+    const uint32_t *key_len;
+    const uint8_t *store;
+    const uint64_t *val_off;
+    const uint32_t *val_size;
+    uint8_t *enc;
+    const uint32_t *val_len;
+    uint32_t count;
+    const int64_t *item_time;
+    const int32_t *item_ttl;
+    int64_t now;
+    int64_t *last_access;
+    uint32_t max_val_len;
+    int reply_header;
+    uint8_t *frame;
+    uint64_t max_response;
+    uint64_t *frame_len;
+    uint64_t *result;
+    /* work area (lzf_mget_carve).  g_*: the entries' descriptors in list order
+     * (a dropped entry: g_enc NULL; g_null: the item an expired entry nulls);
+     * w_*: as LzfFrameArgs, and per tile the frame bytes and the three counts */
+    uint64_t *w_state, *g_key_off, *g_val_off, *w_off, *w_voff, *w_tile, *w_tcnt;
+    uint32_t *g_key_len, *g_val_size, *g_val_len, *g_null, *w_len;
+    int32_t *w_err;
+    uint8_t *g_enc, *w_skip;
+};
+
 /* compress scratch of the lane generation (lzf_lane.hip), device pointers:
  * per value cstride u16 cand words and bstride u32 inserted-bitmap words */
 struct LzfLaneScratch {
@@ -167,6 +216,21 @@ hipError_t lzf_launch_store_usage(LzfCompactArgs &a, hipStream_t s);
 hipError_t lzf_launch_store_compact(LzfCompactArgs &a, hipStream_t s);
 uint64_t lzf_compact_work_bytes(uint32_t count);
 void lzf_compact_carve(LzfCompactArgs &a, void *work);
+/* the operators over the store (lzf_mget.hip): the prefix select into an
+ * index list, and MGET (`decode` over the gathered entries, in place in the
+ * frame), COUNT and MTTL over an index list */
+hipError_t lzf_launch_store_select(LzfSelectArgs &a, hipStream_t s);
+uint64_t lzf_select_work_bytes(uint32_t count);
+void lzf_select_carve(LzfSelectArgs &a, void *work);
+hipError_t lzf_launch_store_mget(LzfMgetArgs &a, hipStream_t s, hipError_t (*decode)(const LzfBatch &, hipStream_t));
+uint64_t lzf_mget_work_bytes(uint32_t n);
+void lzf_mget_carve(LzfMgetArgs &a, void *work);
+hipError_t lzf_launch_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
+                                  const int64_t *item_time, const int32_t *item_ttl, int64_t now, int64_t *last_access,
+                                  uint64_t *result, hipStream_t s);
+hipError_t lzf_launch_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *enc, uint32_t count,
+                                 int64_t *item_time, int32_t *item_ttl, int64_t now, int64_t *last_access,
+                                 uint64_t *result, hipStream_t s);
 /* value moves between mapped host memory and device arenas (lzf_hostio.hip):
  * len[k] (at least min_len) bytes from src + src_off[k] to dst + dst_off[k] */
 hipError_t lzf_launch_move(const uint8_t *src, const uint64_t *src_off, uint8_t *dst, const uint64_t *dst_off,

@@ -57,7 +57,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "lzf_internal.h"
+#include "lzf_dev.h"
 #include "gb_policy.h"
 #include "../../include/lzf_gpu.h"
 
@@ -92,35 +92,6 @@ namespace {
 /* state words of the work area */
 enum { ST_EWORK = 0, ST_BASE = 1, ST_TOTAL = 2, ST_STATUS = 3 };
 
-__device__ inline uint64_t st_shfl_up64(uint64_t x, int d)
-{
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, d, 64);
-    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-/* block-wide exclusive scan of one u64 per thread: an inclusive wave scan,
- * then the totals of the waves before this one; sw: ST_WAVES words of LDS */
-__device__ inline uint64_t st_block_excl(uint64_t x, uint64_t *sw, uint64_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = st_shfl_up64(inc, d);
-        if (lane >= (uint32_t)d) inc += o;
-    }
-    if (lane == 63u) sw[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0ull, all = 0ull;
-    for (uint32_t w = 0; w < ST_WAVES; w++) {
-        if (w < wave) before += sw[w];
-        all += sw[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + inc - x;
-}
-
 /* what the scan of step 1 (SIZE false: the cap of a candidate, 0 otherwise)
  * and of step 3 (SIZE true: the stored size) adds up */
 template <bool SIZE>
@@ -146,7 +117,7 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_store_reduce_kernel(LzfStoreArgs
     for (uint32_t k = 0; k < ST_PER; k++)
         if (first + k < a.count) s += st_item<SIZE>(a, first + k, ework);
     uint64_t tot;
-    (void)st_block_excl(s, sw, &tot);
+    (void)dv_block_excl<ST_WAVES>(s, sw, &tot);
     if (threadIdx.x == 0u) a.w_tile[blockIdx.x] = tot;
 }
 
@@ -161,7 +132,7 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_store_carry_kernel(LzfStoreArgs 
         const uint32_t i = c + threadIdx.x;
         const uint64_t x = i < ntile ? a.w_tile[i] : 0ull;
         uint64_t tot;
-        const uint64_t o = st_block_excl(x, sw, &tot);
+        const uint64_t o = dv_block_excl<ST_WAVES>(x, sw, &tot);
         if (i < ntile) a.w_tile[i] = run + o;
         run += tot;
     }
@@ -195,7 +166,7 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_store_write_kernel(LzfStoreArgs 
         s += v[k];
     }
     uint64_t tot;
-    uint64_t o = st_block_excl(s, sw, &tot) + a.w_tile[blockIdx.x];
+    uint64_t o = dv_block_excl<ST_WAVES>(s, sw, &tot) + a.w_tile[blockIdx.x];
     if (SIZE) o += a.w_state[ST_BASE];
 #pragma unroll
     for (uint32_t k = 0; k < ST_PER; k++) {
@@ -528,8 +499,8 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_compact_reduce_kernel(LzfCompact
         }
     }
     uint64_t tot, dtot;
-    (void)st_block_excl(s, sw, &tot);
-    (void)st_block_excl(dead, sw, &dtot);
+    (void)dv_block_excl<ST_WAVES>(s, sw, &tot);
+    (void)dv_block_excl<ST_WAVES>(dead, sw, &dtot);
     if (RANGE) bad = __syncthreads_or(bad);
     if (threadIdx.x != 0u) return;
     a.w_tile_n[blockIdx.x] = (tot >> 48) | (bad ? ST_TILE_BAD : 0ull);
@@ -553,8 +524,8 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_compact_carry_kernel(LzfCompactA
         bad |= (int)(xn >> 63);
         xn &= ~ST_TILE_BAD;
         uint64_t tn, tb, td;
-        const uint64_t on = st_block_excl(xn, sw, &tn), ob = st_block_excl(xb, sw, &tb);
-        (void)st_block_excl(xd, sw, &td);
+        const uint64_t on = dv_block_excl<ST_WAVES>(xn, sw, &tn), ob = dv_block_excl<ST_WAVES>(xb, sw, &tb);
+        (void)dv_block_excl<ST_WAVES>(xd, sw, &td);
         if (COMPACT && i < ntile) {
             a.w_tile_n[i] = rn + on;
             a.w_tile_b[i] = rb + ob;
@@ -598,7 +569,7 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_compact_write_kernel(LzfCompactA
         s += v[k];
     }
     uint64_t tot;
-    const uint64_t o = st_block_excl(s, sw, &tot);
+    const uint64_t o = dv_block_excl<ST_WAVES>(s, sw, &tot);
     uint64_t rank = a.w_tile_n[blockIdx.x] + (o >> 48);
     uint64_t off = a.w_state[ST_BASE] + a.w_tile_b[blockIdx.x] + (o & ST_LIVE_BYTES);
 #pragma unroll

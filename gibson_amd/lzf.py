@@ -57,6 +57,12 @@ EXPORTS = (
     "lzf_gpu_store_usage",
     "lzf_gpu_store_compact_work_size",
     "lzf_gpu_store_compact",
+    "lzf_gpu_store_select_work_size",
+    "lzf_gpu_store_select_prefix",
+    "lzf_gpu_store_mget_work_size",
+    "lzf_gpu_store_mget",
+    "lzf_gpu_store_count",
+    "lzf_gpu_store_mttl",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -67,6 +73,8 @@ KIND_COMPRESS, KIND_DECOMPRESS = 0, 1
 STORE_OK, STORE_FULL, STORE_EWORK = 0, 1, 2
 # *status of store_compact only: a live item's bytes leave the source arena
 STORE_ERANGE = 3
+# result[3] of store_mget (include/lzf_gpu.h)
+MGET_OK, MGET_NOT_FOUND, MGET_TOO_BIG, MGET_EDECODE = 0, 1, 2, 3
 
 # item encodings (src/net.h:274-278) and the MGET reply code (src/query.h:71)
 ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
@@ -176,6 +184,8 @@ def _load(path):
         _bind_store(L)
     if hasattr(L, "lzf_gpu_store_compact"):
         _bind_store_lifecycle(L)
+    if hasattr(L, "lzf_gpu_store_mget"):
+        _bind_store_index(L)
     del i32
     _LOADED[path] = L
     return L
@@ -235,6 +245,26 @@ def _bind_store_lifecycle(L):
     L.lzf_gpu_store_compact_work_size.argtypes = [u32]
     L.lzf_gpu_store_compact.restype = ctypes.c_int
     L.lzf_gpu_store_compact.argtypes = [vp, u64, vp, vp, vp, u32, vp, u64, vp, vp, vp, vp, vp]
+
+
+def _bind_store_index(L):
+    """The prefix select and the index-list operators (MGET, COUNT, MTTL) of
+    the device store; absent from an older build given by LZF_HIP_LIB (the
+    helpers below then raise AttributeError)."""
+    u32, u64, vp, i64, i32 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    L.lzf_gpu_store_select_work_size.restype = u64
+    L.lzf_gpu_store_select_work_size.argtypes = [u32]
+    L.lzf_gpu_store_select_prefix.restype = ctypes.c_int
+    L.lzf_gpu_store_select_prefix.argtypes = [vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp]
+    L.lzf_gpu_store_mget_work_size.restype = u64
+    L.lzf_gpu_store_mget_work_size.argtypes = [u32]
+    L.lzf_gpu_store_mget.restype = ctypes.c_int
+    L.lzf_gpu_store_mget.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, i64, vp, u32, ctypes.c_int,
+                                     vp, u64, vp, vp, vp, vp]
+    L.lzf_gpu_store_count.restype = ctypes.c_int
+    L.lzf_gpu_store_count.argtypes = [vp, u32, vp, u32, vp, vp, i64, vp, vp, vp]
+    L.lzf_gpu_store_mttl.restype = ctypes.c_int
+    L.lzf_gpu_store_mttl.argtypes = [vp, u32, i32, vp, u32, vp, vp, i64, vp, vp, vp]
 
 
 def selfcheck():
@@ -555,6 +585,87 @@ def store_compact(src, val_off, val_size, enc, dst, dst_used, report, status, wo
                                      _ptr(work), _stream_handle(stream))
     _check(rc, "lzf_gpu_store_compact")
     return work
+
+
+# ---- prefix operators over the device store -----------------------------------
+
+def _opt_ptr(t):
+    return ctypes.c_void_p(0) if t is None else _ptr(t)
+
+
+def store_select_work(count, device):
+    """A scratch tensor for one store_select_prefix call over ``count`` items."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_select_work_size(int(count))), dtype=torch.uint8, device=device)
+
+
+def store_select_prefix(keys, key_off, key_len, enc, prefix, sel, result, work=None, stream=None):
+    """tr_search on the device: sel (int32, read as u32; its length is the cap)
+    receives, in ascending order, the indices of the items that are not
+    ENC_NULL and whose key starts with ``prefix`` (a uint8 tensor on the
+    device), padded with 0xFFFFFFFF (-1); result (2 elements, int32) = [min(matches,
+    cap), matches].  Expired items match too: the consuming operator drops
+    them.  Index order is not the reference's trie order (include/lzf_gpu.h).
+    No host wait; returns ``work`` (store_select_work), which must outlive the
+    stream's work."""
+    n = enc.numel()
+    if work is None:
+        work = store_select_work(n, enc.device)
+    rc = lib().lzf_gpu_store_select_prefix(_ptr(keys), _ptr(key_off), _ptr(key_len), _ptr(enc), n, _ptr(prefix),
+                                           int(prefix.numel()), _ptr(sel), int(sel.numel()), _ptr(result),
+                                           _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_select_prefix")
+    return work
+
+
+def store_mget_work(n, device):
+    """A scratch tensor for one store_mget call over a list of ``n`` entries."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_mget_work_size(int(n))), dtype=torch.uint8, device=device)
+
+
+def store_mget(idx, keys, key_off, key_len, store, val_off, val_size, enc, val_len, item_time, item_ttl, now,
+               max_val_len, frame, max_response, frame_len, result, last_access=None, work=None, reply_header=True,
+               stream=None):
+    """MGET over the index list ``idx`` (int32, read as u32; entries past
+    enc's length are ignored): dead and expired entries drop out, expired ones
+    become ENC_NULL in enc, valid ones get last_access = now, and the reply
+    frame of kv_frame is built over the valid entries in list order with the
+    element count taken on the device.  item_time (int64) and item_ttl (int32)
+    may both be None: nothing expires.  result (4 elements, int64) = found,
+    expired, skipped, MGET_*; frame_len (1 element, int64) is 0 unless
+    MGET_OK.  No host wait; returns ``work`` (store_mget_work), which must
+    outlive the stream's work."""
+    n = idx.numel()
+    if work is None:
+        work = store_mget_work(n, frame.device)
+    rc = lib().lzf_gpu_store_mget(_ptr(idx), n, _ptr(keys), _ptr(key_off), _ptr(key_len), _ptr(store), _ptr(val_off),
+                                  _ptr(val_size), _ptr(enc), _ptr(val_len), int(enc.numel()), _opt_ptr(item_time),
+                                  _opt_ptr(item_ttl), int(now), _opt_ptr(last_access), int(max_val_len),
+                                  1 if reply_header else 0, _ptr(frame), int(max_response), _ptr(frame_len),
+                                  _ptr(result), _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_mget")
+    return work
+
+
+def store_count(idx, enc, item_time, item_ttl, now, result, last_access=None, stream=None):
+    """COUNT over an index list: result (2 elements, int64) = valid entries,
+    entries this call expired (and nulled in enc); valid entries get
+    last_access = now.  MDEL is store_count followed by store_delete over the
+    same list.  No host wait."""
+    _check(lib().lzf_gpu_store_count(_ptr(idx), int(idx.numel()), _ptr(enc), int(enc.numel()), _opt_ptr(item_time),
+                                     _opt_ptr(item_ttl), int(now), _opt_ptr(last_access), _ptr(result),
+                                     _stream_handle(stream)), "lzf_gpu_store_count")
+
+
+def store_mttl(idx, ttl, enc, item_time, item_ttl, now, result, last_access=None, stream=None):
+    """MTTL over an index list of distinct entries: a valid entry gets
+    item_time = last_access = now and item_ttl = ttl (already clamped to
+    maxitemttl); result (2 elements, int64) = entries changed, entries this
+    call expired.  No host wait."""
+    _check(lib().lzf_gpu_store_mttl(_ptr(idx), int(idx.numel()), int(ttl), _ptr(enc), int(enc.numel()),
+                                    _ptr(item_time), _ptr(item_ttl), int(now), _opt_ptr(last_access), _ptr(result),
+                                    _stream_handle(stream)), "lzf_gpu_store_mttl")
 
 
 def host_register(arr):

@@ -423,6 +423,123 @@ int lzf_gpu_store_compact(const uint8_t *src, uint64_t src_cap,
                           uint8_t *dst, uint64_t dst_cap, uint64_t *dst_used,
                           uint64_t *report, uint32_t *status, void *work, void *stream);
 
+/*
+ * Prefix operators over the device store: select, MGET, COUNT, MTTL.
+ *
+ * Every multi-key operator of the reference is tr_search over a prefix plus a
+ * callback per item found (src/query.c:526, 620, 687, 1171).  Here the search
+ * is lzf_gpu_store_select_prefix, which leaves an index list in device
+ * memory, and the callbacks are the index-list operators below; MDEL is
+ * lzf_gpu_store_count followed by lzf_gpu_store_delete over the same list
+ * (count's result[0] is the reply of gbQueryMultiDelHandler).  Everything
+ * queues on one stream with no host wait.
+ *
+ * The store's per-item arrays, all of `count` entries: val_off, val_size, enc
+ * (lzf_gpu_set_store), val_len (the original lengths, in_len of the SET),
+ * keys / key_off / key_len (as lzf_gpu_kv_frame takes them), item_time (i64)
+ * and item_ttl (i32) (as lzf_gpu_store_expire takes them), and last_access
+ * (i64, optional: NULL is not written).
+ *
+ * Index lists.  idx[n] (u32), n given by the host.  An entry >= count is
+ * ignored by every operator, as by lzf_gpu_store_delete, so 0xFFFFFFFF pads a
+ * list made on the device and no device-side length is needed.
+ *
+ * The validity rule, shared by the three operators (gbIsItemStillValid with
+ * remove = 1, src/query.c:204-224).  An in-range entry i is
+ *   dead     if enc[i] == LZF_ENC_NULL;
+ *   expired  if item_ttl[i] > 0 && now - item_time[i] >= item_ttl[i]; the
+ *            operator then sets enc[i] = LZF_ENC_NULL (the device tr_remove);
+ *   valid    otherwise.
+ * item_time and item_ttl may both be NULL (nothing expires); exactly one of
+ * them NULL is LZF_GPU_EARG.
+ *
+ * Order is a stated limit.  The select yields matches in ascending item
+ * index; the reference's tr_search yields them in trie pre-order with the
+ * children in creation order (src/trie.c:154-176).  COUNT, MTTL, MDEL and
+ * every operator that passes limit = -1 and replies a number do not depend on
+ * the order: select -> operator is exact for them.  MGET with a limit, and
+ * the reply order of MGET and KEYS, do depend on it: for those the index
+ * list must still come from the host's trie.
+ *
+ * LZF_GPU_EARG: a NULL pointer (but the optional ones), count == 0, n == 0,
+ * and what each call names.  count and n: up to 2^32 - 1; all byte arithmetic
+ * is 64-bit.
+ */
+
+/* Item i matches iff enc[i] != LZF_ENC_NULL, key_len[i] >= prefix_len and its
+ * first prefix_len key bytes equal prefix (device memory).  A key equal to the
+ * prefix matches (tr_recurse calls the handler on the start node), and so does
+ * an expired item (tr_search returns it; the consuming operator drops it).
+ * result (2 device u32): [1] the number of matches, [0] min(matches, cap).
+ * sel[0 .. result[0]) holds the matching indices in ascending order,
+ * sel[result[0] .. cap) is filled with 0xFFFFFFFF.  prefix_len == 0 or
+ * cap == 0: LZF_GPU_EARG.  work: lzf_gpu_store_select_work_size(count) bytes
+ * of device scratch that must stay valid until the stream's work is done. */
+uint64_t lzf_gpu_store_select_work_size(uint32_t count);
+int lzf_gpu_store_select_prefix(const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                                const uint8_t *enc, uint32_t count,
+                                const uint8_t *prefix, uint32_t prefix_len,
+                                uint32_t *sel, uint32_t cap, uint32_t *result /* 2 u32 */,
+                                void *work, void *stream);
+
+/*
+ * MGET over an index list: what gbQueryMultiGetHandler does after tr_search
+ * (src/query.c:688-706), for the entries of idx in list order.  Dead and
+ * expired entries drop out, expired ones are nulled in enc, every valid entry
+ * gets last_access[i] = now, and `found` is the number of valid entries.  The
+ * payload of gbClientEnqueueKeyValueSet is then built over the valid entries
+ * with elements = found, taken on the device: exactly the bytes
+ * lzf_gpu_kv_frame writes for the same items in the same order, LZF items
+ * decoded straight into the frame.
+ *
+ * result (4 device u64): [0] found, [1] the entries this call expired, [2] the
+ * entries skipped as dead or out of range, [3] one of LZF_MGET_*.
+ * *frame_len: the frame's byte count on LZF_MGET_OK, otherwise 0.  frame must
+ * hold (reply_header ? 7 : 0) + max_response bytes; no byte at or past that
+ * is ever written, and none at all on NOT_FOUND or TOO_BIG.  The nulling and
+ * last_access happen whatever the status is, as in the reference, where the
+ * validity pass runs before the reply is built.  A duplicated entry is treated
+ * on its own each time, emitted twice and counted twice, judged on what enc
+ * held before the call.  max_val_len bounds val_len of the LZF items
+ * (above LZF_GPU_MAX_VALUE: LZF_GPU_EARG).  work:
+ * lzf_gpu_store_mget_work_size(n) bytes of device scratch that must stay valid
+ * until the stream's work is done.
+ */
+#define LZF_MGET_OK         0
+#define LZF_MGET_NOT_FOUND  1   /* no valid item: the host replies REPL_ERR_NOT_FOUND (src/query.c:731-735) */
+#define LZF_MGET_TOO_BIG    2   /* payload > max_response: CHECK_SPACE, src/net.c:1272-1277 */
+#define LZF_MGET_EDECODE    3   /* an LZF item did not decode to val_len */
+
+uint64_t lzf_gpu_store_mget_work_size(uint32_t n);
+int lzf_gpu_store_mget(const uint32_t *idx, uint32_t n,
+                       const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                       const uint8_t *store, const uint64_t *val_off, const uint32_t *val_size,
+                       uint8_t *enc, const uint32_t *val_len, uint32_t count,
+                       const int64_t *item_time, const int32_t *item_ttl, int64_t now,
+                       int64_t *last_access /* may be NULL */,
+                       uint32_t max_val_len, int reply_header,
+                       uint8_t *frame, uint64_t max_response, uint64_t *frame_len,
+                       uint64_t *result /* 4 u64 */, void *work, void *stream);
+
+/* COUNT, gbCountCallback (src/query.c:1139-1157): the validity rule over the
+ * list, last_access[i] = now for the valid entries; result (2 device u64):
+ * [0] the valid entries -- 0 is an ordinary result, the reference replies
+ * REPL_VAL 0 -- and [1] the entries this call expired.  Entries should be
+ * distinct, as a trie walk or a select yields them: a duplicate is counted
+ * each time it is valid, and a duplicated expired entry is counted as expired
+ * at least once. */
+int lzf_gpu_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
+                        const int64_t *item_time, const int32_t *item_ttl, int64_t now,
+                        int64_t *last_access, uint64_t *result /* 2 u64: valid, expired */, void *stream);
+/* MTTL, gbMultiTtlCallback (src/query.c:580-600): a valid entry gets
+ * item_time[i] = last_access[i] = now and item_ttl[i] = ttl, which the caller
+ * has clamped to maxitemttl.  The time arrays must not be NULL.  result
+ * (2 device u64): [0] the entries changed, [1] the entries this call expired.
+ * Entries must be distinct; a duplicate is memory-safe, its count unspecified. */
+int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *enc, uint32_t count,
+                       int64_t *item_time, int32_t *item_ttl, int64_t now,
+                       int64_t *last_access, uint64_t *result /* 2 u64: changed, expired */, void *stream);
+
 /* Free the library's device scratch (all devices), the calling thread's and
  * the device workers' staging buffers; later calls allocate them again.
  * Each thread's staging buffers are also freed when the thread exits. */
