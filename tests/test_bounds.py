@@ -1,8 +1,8 @@
 """Nothing is written outside a value's output range (needs a GPU).
 
 Every value's output region out[out_off, out_off + out_cap) is followed by a
-guard gap; the arena starts as a canary pattern.  After compress (server
-caps, tight caps, failing caps) and decompress (valid, E2BIG, EINVAL
+guard gap, and the first one preceded by one; the arena starts as a canary
+pattern.  After compress (server caps, tight caps, failing caps) and decompress (valid, E2BIG, EINVAL
 streams) every guard byte is unchanged.  A batch whose stated max length is
 below a value's length (a caller contract violation) refuses that value --
 out_len 0 (and EINVAL on decompress) -- and leaves its region untouched
@@ -33,7 +33,7 @@ def _lane_for_any_batch(monkeypatch):
 
 
 def _layout(caps):
-    offs, pos = [], 0
+    offs, pos = [], GUARD                # a band before the first region too: an underrun of region 0
     for c in caps:
         offs.append(pos)
         pos += c + GUARD
@@ -62,6 +62,8 @@ def _run_compress(vals, caps, max_len):
 
 
 def _guards_intact(out, offs, caps):
+    if offs[0] != GUARD or not (out[:GUARD] == CANARY).all():
+        return False
     for o, c in zip(offs, caps):
         g = out[o + c:o + c + GUARD]
         if not (g == CANARY).all():
@@ -181,3 +183,108 @@ def test_decompress_refuses_cap_past_stated_max(oracle):
             assert (out[o:o + c + GUARD] == CANARY).all()
         else:
             assert bytes(out[o:o + ln]) == v and e == 0
+
+
+# ---- the decoder's routes, one by one ---------------------------------------
+
+# the batch's stated max_out_cap -> the route lzf_launch_decompress takes and
+# the crafted batch (tests/lzf_tokens.py) whose cases fit under it
+DECODE_ROUTES = {256: "w256", 1024: "w1024", 4096: "w4096", 9000: "far", 16384: "far", 20000: "pipe"}
+
+
+def _period1_run(rnd, max_cap):
+    """a literal and 264-byte references at distance 1 behind it (one byte
+    repeated: the CD_PERIOD shortcut), with caps that end inside the run"""
+    from tests.lzf_tokens import lit, ref
+    k = max(1, min(40, (max_cap - 4) // 264))
+    s = lit(rnd.randbytes(rnd.randint(1, 4))) + ref(264, 1) * k
+    top = min(max_cap, 4 + 264 * k)
+    return [(s, c) for c in (top, top - 1, rnd.randint(5, top), rnd.randint(5, top), 5 + 264 * rnd.randrange(k))]
+
+
+@pytest.mark.parametrize("max_cap", sorted(DECODE_ROUTES))
+def test_decompress_guards_by_route(oracle, max_cap):
+    from tests.lzf_tokens import route_cases
+    rnd = random.Random(0xB0 + max_cap)
+    streams, caps = [], []
+    for i in range(160):                                         # compressor streams, as above
+        n = rnd.choice([max_cap, rnd.randint(1, max_cap)])
+        v = synth(rnd.randrange(6), 0x5EED0B40, i, n)
+        s = oracle.compress(v, n + n // 16 + 64)
+        kind = rnd.randrange(4)
+        if kind == 1:
+            s = s[:rnd.randrange(1, len(s))]                     # EINVAL (truncated)
+        elif kind == 2:
+            b = bytearray(s)
+            b[rnd.randrange(len(b))] = rnd.randrange(256)       # corrupted
+            s = bytes(b)
+        streams.append(s)
+        caps.append(n if kind != 3 else rnd.randint(1, max(1, n - 1)))   # E2BIG
+    crafted = [(s, c, label) for s, c, label in route_cases(DECODE_ROUTES[max_cap]) if c <= max_cap]
+    labels = {label for _, _, label in crafted}
+    assert len(crafted) >= 200 and {"cap-in-lit", "cap-in-ref", "back", "cut+cap", "two-errors"} <= labels
+    for s, c, _ in crafted:
+        streams.append(s)
+        caps.append(c)
+    for _ in range(4):
+        for s, c in _period1_run(rnd, max_cap):
+            streams.append(s)
+            caps.append(c)
+    assert max(caps) == max_cap
+    order = list(range(len(streams)))
+    rnd.shuffle(order)
+    # region 0, behind the leading guard: a back-reference to one byte before the output start
+    first = 160 + next(i for i, (_, c, label) in enumerate(crafted) if label == "back" and c > max_cap // 2)
+    order.remove(first)
+    order.insert(0, first)
+    streams, caps = [streams[i] for i in order], [caps[i] for i in order]
+    expect = [oracle.decompress(s, c) for s, c in zip(streams, caps)]
+    assert {e for _, e in expect} == {0, 7, 22}
+    out, offs, olen, err = _run_decompress(streams, caps, max_cap)
+    assert _guards_intact(out, offs, caps)
+    bad = [(i, len(s), c, exp[1], int(ln), int(e)) for i, (s, c, o, ln, e, exp)
+           in enumerate(zip(streams, caps, offs, olen, err, expect))
+           if (bytes(out[o:o + ln]) if ln else None, int(e)) != exp]
+    assert not bad, (len(bad), bad[:5])
+
+
+# ---- the compressor's other routes ------------------------------------------
+
+def _cap_choices(oracle, rnd, v):
+    n = len(v)
+    full = oracle.compress(v, n + n // 16 + 64)
+    F = len(full) if full else n
+    return max(1, rnd.choice([n - 4, F - 1, F, F + 1, rnd.randint(1, n + 8), F // 2]))
+
+
+def test_compress_guards_on_window64_by_default(oracle, monkeypatch):
+    # the product thresholds (LZF_GPU_LANE_MIN unset): a batch this small goes to window64
+    import re
+    import gibson_amd
+    monkeypatch.delenv("LZF_GPU_LANE_MIN", raising=False)
+    monkeypatch.delenv("LZF_GPU_KERNEL", raising=False)
+    rnd = random.Random(64)
+    vals = [synth(rnd.randrange(6), 0x5EED0B50, i, rnd.choice([4096, rnd.randint(1, 4096), rnd.randint(1, 200)]))
+            for i in range(200)]
+    caps = [_cap_choices(oracle, rnd, v) for v in vals]
+    out, offs, olen = _run_compress(vals, caps, 4096)
+    m = re.search(r"window64 past 64 KiB or below (\d+) values of <= 4 KiB", gibson_amd.kernel_info())
+    assert m and int(m.group(1)) > len(vals), gibson_amd.kernel_info()
+    assert _guards_intact(out, offs, caps)
+    for v, c, o, ln in zip(vals, caps, offs, olen):
+        assert (bytes(out[o:o + ln]) if ln else None) == oracle.compress(v, c)
+
+
+def test_compress_guards_past_64k(oracle):
+    # a value past 64 KiB takes the whole batch to window64 with 64-bit bucket heads
+    import gibson_amd
+    rnd = random.Random(65537)
+    sizes = [65537, 70000, 65536, 1, 100, 4096] + [rnd.randint(1, 70000) for _ in range(34)]
+    rnd.shuffle(sizes)
+    vals = [synth(rnd.randrange(6), 0x5EED0B60, i, n) for i, n in enumerate(sizes)]
+    caps = [_cap_choices(oracle, rnd, v) for v in vals]
+    out, offs, olen = _run_compress(vals, caps, 70000)
+    assert "window64 past 64 KiB" in gibson_amd.kernel_info()
+    assert _guards_intact(out, offs, caps)
+    for v, c, o, ln in zip(vals, caps, offs, olen):
+        assert (bytes(out[o:o + ln]) if ln else None) == oracle.compress(v, c)
