@@ -960,6 +960,57 @@ int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *en
     return e == hipSuccess ? LZF_GPU_OK : code_of(e);
 }
 
+uint64_t lzf_gpu_key_index_bytes(uint32_t slots)
+{
+    return lzf_kidx_slots_ok(slots) ? lzf_kidx_table_bytes(slots) : 0ull;
+}
+
+uint32_t lzf_host_key_home(const uint8_t *key, uint32_t len, uint32_t slots)
+{
+    if (!lzf_kidx_slots_ok(slots) || (!key && len)) return 0xFFFFFFFFu;
+    return lzf_kidx_home(key, len, slots);
+}
+
+int lzf_gpu_key_index_insert(void *table, uint32_t slots, uint32_t *used,
+                             const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                             uint8_t *enc, uint32_t count, uint32_t first, uint32_t n,
+                             uint64_t *result, uint32_t *status, void *stream)
+{
+    if (!table || !used || !keys || !key_off || !key_len || !enc || !result || !status) return LZF_GPU_EARG;
+    if (!count || !n || (uint64_t)first + n > count) return LZF_GPU_EARG;
+    if (!lzf_kidx_slots_ok(slots) || ((uintptr_t)table & 7u)) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfKidxArgs a{};
+    a.table = table; a.slots = slots; a.used = used;
+    a.keys = keys; a.key_off = key_off; a.key_len = key_len;
+    a.enc = enc; a.count = count; a.first = first; a.n = n;
+    a.result = result; a.status = status;
+    const hipError_t e = lzf_launch_kidx_insert(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_gpu_key_index_lookup(const void *table, uint32_t slots,
+                             const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                             const uint8_t *enc, uint32_t count,
+                             const uint8_t *qkeys, const uint64_t *q_off, const uint32_t *q_len, uint32_t nq,
+                             uint32_t *idx, uint64_t *result, void *stream)
+{
+    if (!table || !keys || !key_off || !key_len || !enc || !qkeys || !q_off || !q_len || !idx || !result)
+        return LZF_GPU_EARG;
+    if (!count || !nq) return LZF_GPU_EARG;
+    if (!lzf_kidx_slots_ok(slots) || ((uintptr_t)table & 7u)) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfKidxArgs a{};
+    a.table = const_cast<void *>(table); a.slots = slots;  /* the lookup only reads */
+    a.keys = keys; a.key_off = key_off; a.key_len = key_len;
+    a.enc = const_cast<uint8_t *>(enc); a.count = count;
+    a.result = result;
+    const hipError_t e = lzf_launch_kidx_lookup(a, qkeys, q_off, q_len, nq, idx, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
 int lzf_gpu_selfcheck(void)
 {
     int rc = current_device_ok();

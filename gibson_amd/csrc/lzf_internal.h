@@ -142,6 +142,21 @@ struct LzfMgetArgs {
     uint8_t *g_enc, *w_skip;
 };
 
+/* the key index over the store's keys (lzf_kidx.hip); device pointers.  The
+ * lookup reads table, slots, the key arrays, enc, count and result only */
+struct LzfKidxArgs {
+    void *table;
+    uint32_t slots;
+    uint32_t *used;
+    const uint8_t *keys;
+    const uint64_t *key_off;
+    const uint32_t *key_len;
+    uint8_t *enc;
+    uint32_t count, first, n;
+    uint64_t *result;
+    uint32_t *status;
+};
+
 /* compress scratch of the lane generation (lzf_lane.hip), device pointers:
  * per value cstride u16 cand words and bstride u32 inserted-bitmap words */
 struct LzfLaneScratch {
@@ -231,6 +246,15 @@ hipError_t lzf_launch_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc,
 hipError_t lzf_launch_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *enc, uint32_t count,
                                  int64_t *item_time, int32_t *item_ttl, int64_t now, int64_t *last_access,
                                  uint64_t *result, hipStream_t s);
+/* the key index (lzf_kidx.hip): the table's geometry and a key's home slot on
+ * the host, the upsert of the items [first, first + n) and the lookup of nq
+ * query keys into idx */
+bool lzf_kidx_slots_ok(uint32_t slots);
+uint64_t lzf_kidx_table_bytes(uint32_t slots);
+uint32_t lzf_kidx_home(const uint8_t *key, uint32_t len, uint32_t slots);
+hipError_t lzf_launch_kidx_insert(LzfKidxArgs &a, hipStream_t s);
+hipError_t lzf_launch_kidx_lookup(LzfKidxArgs &a, const uint8_t *qkeys, const uint64_t *q_off, const uint32_t *q_len,
+                                  uint32_t nq, uint32_t *idx, hipStream_t s);
 /* value moves between mapped host memory and device arenas (lzf_hostio.hip):
  * len[k] (at least min_len) bytes from src + src_off[k] to dst + dst_off[k] */
 hipError_t lzf_launch_move(const uint8_t *src, const uint64_t *src_off, uint8_t *dst, const uint64_t *dst_off,

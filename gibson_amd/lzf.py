@@ -63,6 +63,10 @@ EXPORTS = (
     "lzf_gpu_store_mget",
     "lzf_gpu_store_count",
     "lzf_gpu_store_mttl",
+    "lzf_gpu_key_index_bytes",
+    "lzf_host_key_home",
+    "lzf_gpu_key_index_insert",
+    "lzf_gpu_key_index_lookup",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -75,6 +79,8 @@ STORE_OK, STORE_FULL, STORE_EWORK = 0, 1, 2
 STORE_ERANGE = 3
 # result[3] of store_mget (include/lzf_gpu.h)
 MGET_OK, MGET_NOT_FOUND, MGET_TOO_BIG, MGET_EDECODE = 0, 1, 2, 3
+# *status of key_index_insert (include/lzf_gpu.h)
+KIDX_OK, KIDX_FULL = 0, 1
 
 # item encodings (src/net.h:274-278) and the MGET reply code (src/query.h:71)
 ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
@@ -186,6 +192,8 @@ def _load(path):
         _bind_store_lifecycle(L)
     if hasattr(L, "lzf_gpu_store_mget"):
         _bind_store_index(L)
+    if hasattr(L, "lzf_gpu_key_index_insert"):
+        _bind_key_index(L)
     del i32
     _LOADED[path] = L
     return L
@@ -265,6 +273,20 @@ def _bind_store_index(L):
     L.lzf_gpu_store_count.argtypes = [vp, u32, vp, u32, vp, vp, i64, vp, vp, vp]
     L.lzf_gpu_store_mttl.restype = ctypes.c_int
     L.lzf_gpu_store_mttl.argtypes = [vp, u32, i32, vp, u32, vp, vp, i64, vp, vp, vp]
+
+
+def _bind_key_index(L):
+    """The device key index; absent from an older build given by LZF_HIP_LIB
+    (the helpers below then raise AttributeError)."""
+    u32, u64, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
+    L.lzf_gpu_key_index_bytes.restype = u64
+    L.lzf_gpu_key_index_bytes.argtypes = [u32]
+    L.lzf_host_key_home.restype = u32
+    L.lzf_host_key_home.argtypes = [vp, u32, u32]
+    L.lzf_gpu_key_index_insert.restype = ctypes.c_int
+    L.lzf_gpu_key_index_insert.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
+    L.lzf_gpu_key_index_lookup.restype = ctypes.c_int
+    L.lzf_gpu_key_index_lookup.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp]
 
 
 def selfcheck():
@@ -666,6 +688,61 @@ def store_mttl(idx, ttl, enc, item_time, item_ttl, now, result, last_access=None
     _check(lib().lzf_gpu_store_mttl(_ptr(idx), int(idx.numel()), int(ttl), _ptr(enc), int(enc.numel()),
                                     _ptr(item_time), _ptr(item_ttl), int(now), _opt_ptr(last_access), _ptr(result),
                                     _stream_handle(stream)), "lzf_gpu_store_mttl")
+
+
+# ---- the device key index: exact-key lookup and upsert -------------------------
+
+def key_index_bytes(slots):
+    """lzf_gpu_key_index_bytes(): the table's size for ``slots`` slots, a power
+    of two in [16, 2**31].  A tensor of that many bytes filled with 0xFF is an
+    empty table."""
+    b = int(lib().lzf_gpu_key_index_bytes(int(slots)))
+    if not b:
+        raise ValueError(f"key_index_bytes: bad slots {slots}")
+    return b
+
+
+def key_home(key_bytes, slots):
+    """lzf_host_key_home(): the home slot of a key; its probe sequence is
+    home, home + 1, ... modulo ``slots``.  No GPU."""
+    key = bytes(key_bytes)
+    h = int(lib().lzf_host_key_home(ctypes.c_char_p(key), len(key), int(slots)))
+    if h == 0xFFFFFFFF:
+        raise ValueError(f"key_home: bad slots {slots}")
+    return h
+
+
+def _key_index_slots(table):
+    return int(table.numel() * table.element_size() // 8)
+
+
+def key_index_insert(table, used, keys, key_off, key_len, enc, first, n, result, status, stream=None):
+    """Upsert of the store's items [first, first + n) into ``table`` (a tensor
+    of key_index_bytes(slots) bytes; slots is taken from its size), in request
+    order: among equal keys of the batch the highest index stays and the
+    others become ENC_NULL, and a live item that held the key before becomes
+    ENC_NULL.  used (1 element, int32) counts claimed slots and is zeroed
+    with the table; result (4 elements, int64) = mapped, replaced, superseded,
+    skipped; status (1 element, int32) = KIDX_OK, or KIDX_FULL with the batch
+    refused whole and nothing changed.  keys uint8, key_off int64, key_len
+    int32, enc uint8, on one device.  No host wait."""
+    rc = lib().lzf_gpu_key_index_insert(_ptr(table), _key_index_slots(table), _ptr(used), _ptr(keys), _ptr(key_off),
+                                        _ptr(key_len), _ptr(enc), int(enc.numel()), int(first), int(n), _ptr(result),
+                                        _ptr(status), _stream_handle(stream))
+    _check(rc, "lzf_gpu_key_index_insert")
+
+
+def key_index_lookup(table, keys, key_off, key_len, enc, qkeys, q_off, q_len, idx, result, stream=None):
+    """Lookup of the query keys qkeys / q_off / q_len (as many as q_len has
+    entries): idx (int32, read as u32) receives the item index per key, or
+    0xFFFFFFFF (-1) for an absent key, a dead item or an empty key -- the
+    padding store_mget, store_count, store_delete and store_mttl ignore, so
+    idx feeds them as it is.  result (3 elements, int64) = hits, misses, slots
+    examined.  No host wait."""
+    rc = lib().lzf_gpu_key_index_lookup(_ptr(table), _key_index_slots(table), _ptr(keys), _ptr(key_off), _ptr(key_len),
+                                        _ptr(enc), int(enc.numel()), _ptr(qkeys), _ptr(q_off), _ptr(q_len),
+                                        int(q_len.numel()), _ptr(idx), _ptr(result), _stream_handle(stream))
+    _check(rc, "lzf_gpu_key_index_lookup")
 
 
 def host_register(arr):

@@ -540,6 +540,112 @@ int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *en
                        int64_t *item_time, int32_t *item_ttl, int64_t now,
                        int64_t *last_access, uint64_t *result /* 2 u64: changed, expired */, void *stream);
 
+/*
+ * The device key index: exact-key lookup and upsert for the device store.
+ *
+ * The operators above address items by index.  The key index maps key bytes
+ * to an item index in device memory, so that a request buffer of keys goes in
+ * and an index list comes out with no host lookup: insert is tr_insert plus
+ * gbDestroyItem(old) (src/query.c:418-422) for the items a lzf_gpu_set_store
+ * has just written, lookup is tr_find_node for a batch of query keys.
+ *
+ * The table is caller-owned device memory of lzf_gpu_key_index_bytes(slots)
+ * bytes, 8-byte aligned; slots is a power of two in [16, 2^31] (otherwise the
+ * size is 0 and every call LZF_GPU_EARG).  Its layout is opaque but for two
+ * fixed points: a table filled with byte 0xFF is empty, so
+ * hipMemsetAsync(table, 0xFF, bytes) clears it, and the probe sequence of a
+ * key is home, home + 1, ... modulo slots (linear probing), home being
+ * lzf_host_key_home(key, len, slots).  `used` is one device u32 that the
+ * caller owns and zeroes together with the table; it counts claimed slots.
+ *
+ * A slot names an item index of the store.  Key bytes are never copied into
+ * the table: they are read from keys / key_off / key_len (as lzf_gpu_kv_frame
+ * takes them), which must therefore stay intact for dead items too until the
+ * table is rebuilt.  A slot never returns to empty except by a clear, so
+ * chains never break: the slot of an item that has gone dead (enc[i] ==
+ * LZF_ENC_NULL) keeps its place and a later insert of the same key takes it
+ * over.
+ *
+ * Rebuild: clear the table and *used, then insert [0, count).  Dead items
+ * drop out and *used becomes the number of distinct live keys.  It belongs
+ * with lzf_gpu_store_compact: both are the store's housekeeping, run when
+ * lzf_gpu_store_usage shows enough dead items, and item indices survive both.
+ *
+ * Not modelled: locks -- SET on a locked item replies REPL_ERR_LOCKED
+ * (src/query.c:446-451) and the host still decides that; the single-item GET
+ * reply (gbClientEnqueueItem) -- the lookup yields the index, and the KVAL
+ * frame of lzf_gpu_store_mget is what the device writes; the ordered prefix
+ * walk, which stays with the host's trie.
+ */
+#define LZF_KIDX_OK    0
+#define LZF_KIDX_FULL  1   /* *used + n > slots - slots / 4: the batch was refused as a whole */
+
+uint64_t lzf_gpu_key_index_bytes(uint32_t slots);
+/* host, no HIP call: the home slot the device uses for a key; 0xFFFFFFFF for a
+ * bad `slots`.  For sizing, and for building a chain on purpose. */
+uint32_t lzf_host_key_home(const uint8_t *key, uint32_t len, uint32_t slots);
+
+/*
+ * Upsert of the items [first, first + n) of a store of `count` items.  The
+ * outcome is that of the loop, in ascending i over the batch:
+ *   skip i if enc[i] == LZF_ENC_NULL or key_len[i] == 0 (the reference
+ *   asserts klen > 0); j = map.get(key_i); if j exists, j != i and j is live:
+ *   enc[j] = LZF_ENC_NULL; map[key_i] = i
+ * whatever order the device's threads run in:
+ *   - among batch items with equal keys the highest index ends as the key's
+ *     mapping, the others get enc = LZF_ENC_NULL ("superseded");
+ *   - a batch item always beats an occupant from outside the batch, whatever
+ *     the two indices are (callers may reuse low indices): a live occupant
+ *     gets enc = LZF_ENC_NULL ("replaced"), the slot of a dead one is simply
+ *     taken over, and *used grows in neither case;
+ *   - an occupant that lies in the batch takes part as the batch item it is,
+ *     so inserting a range that is already indexed changes nothing.
+ * result (4 device u64): [0] batch items that are their key's mapping after
+ * the call, [1] replaced, [2] superseded, [3] skipped.  *used grows by the
+ * number of slots newly claimed.
+ *
+ * *status (one device u32): LZF_KIDX_OK, or LZF_KIDX_FULL exactly when
+ * *used + n > slots - slots / 4 (n counted whole, skipped items included),
+ * judged on *used as it was before the call.  Then the batch is refused as a
+ * whole: no table byte, no enc and not *used change, and result is zero.  The
+ * host reads status back with the reply; the remedy is a larger table and a
+ * rebuild.  Until then the batch's items are live in the store but NOT
+ * findable by key -- a lookup misses them and a later SET of the same key
+ * does not replace them.
+ *
+ * LZF_GPU_EARG, before any HIP call: a NULL pointer, count == 0, n == 0,
+ * first + n > count (64-bit arithmetic), a bad `slots`, a table that is not
+ * 8-byte aligned.  Asynchronous on `stream`, with no host wait.
+ */
+int lzf_gpu_key_index_insert(void *table, uint32_t slots, uint32_t *used,
+                             const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                             uint8_t *enc, uint32_t count, uint32_t first, uint32_t n,
+                             uint64_t *result /* 4 u64 */, uint32_t *status, void *stream);
+
+/*
+ * Lookup of nq query keys (qkeys / q_off / q_len, an arena of their own or
+ * the store's).  idx[k] is the item index the key maps to, or 0xFFFFFFFF when
+ * the key is absent, its item is dead, or q_len[k] == 0.  An expired item is a
+ * hit, as tr_find_node returns it: the consuming operator applies the TTL
+ * rule and nulls it, exactly as after a prefix select.  0xFFFFFFFF is the
+ * padding every index-list operator ignores, so idx feeds them unchanged:
+ * lzf_gpu_store_mget is the frame for many exact keys in query order,
+ * lzf_gpu_store_count followed by lzf_gpu_store_delete is DEL by key,
+ * lzf_gpu_store_mttl sets TTLs by key.
+ *
+ * result (3 device u64): [0] hits, [1] misses, [2] slots examined, summed over
+ * the queries (the empty slot that ends a miss counts).  A lookup examines at
+ * most `slots` slots per key, so it terminates on any table contents; a slot
+ * naming an index >= count is a non-matching occupant and is never
+ * dereferenced.  LZF_GPU_EARG: a NULL pointer, count == 0, nq == 0, a bad
+ * `slots`, a table that is not 8-byte aligned.
+ */
+int lzf_gpu_key_index_lookup(const void *table, uint32_t slots,
+                             const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                             const uint8_t *enc, uint32_t count,
+                             const uint8_t *qkeys, const uint64_t *q_off, const uint32_t *q_len, uint32_t nq,
+                             uint32_t *idx, uint64_t *result /* 3 u64 */, void *stream);
+
 /* Free the library's device scratch (all devices), the calling thread's and
  * the device workers' staging buffers; later calls allocate them again.
  * Each thread's staging buffers are also freed when the thread exits. */
