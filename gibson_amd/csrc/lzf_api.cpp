@@ -960,6 +960,102 @@ int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *en
     return e == hipSuccess ? LZF_GPU_OK : code_of(e);
 }
 
+int lzf_gpu_store_mlock(const uint32_t *idx, uint32_t n, int64_t lock_time, uint8_t *enc, uint32_t count,
+                        int64_t *item_time, const int32_t *item_ttl, int64_t *item_lock, int64_t now,
+                        int64_t *last_access, uint8_t *entry_status, uint64_t *result, void *stream)
+{
+    if (!idx || !enc || !item_time || !item_ttl || !item_lock || !result || !n || !count) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfLockArgs a{};
+    a.idx = idx; a.n = n; a.lock_time = lock_time; a.enc = enc; a.count = count;
+    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
+    a.last_access = last_access; a.entry_status = entry_status; a.result = result;
+    const hipError_t e = lzf_launch_store_mlock(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_gpu_store_munlock(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
+                          const int64_t *item_time, const int32_t *item_ttl, int64_t *item_lock, int64_t now,
+                          int64_t *last_access, uint8_t *entry_status, uint64_t *result, void *stream)
+{
+    if (!idx || !enc || !item_time || !item_ttl || !item_lock || !result || !n || !count) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfLockArgs a{};
+    a.idx = idx; a.n = n; a.enc = enc; a.count = count;
+    a.item_time = const_cast<int64_t *>(item_time);        /* MUNLOCK only reads it */
+    a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
+    a.last_access = last_access; a.entry_status = entry_status; a.result = result;
+    const hipError_t e = lzf_launch_store_munlock(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_gpu_store_mdel(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
+                       const int64_t *item_time, const int32_t *item_ttl, const int64_t *item_lock,
+                       int64_t now, uint8_t *entry_status, uint64_t *result, void *stream)
+{
+    if (!idx || !enc || !result || !n || !count) return LZF_GPU_EARG;
+    if (!item_time != !item_ttl || (item_lock && !item_time)) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfLockArgs a{};
+    a.idx = idx; a.n = n; a.enc = enc; a.count = count;
+    a.item_time = const_cast<int64_t *>(item_time);        /* MDEL reads the time arrays only */
+    a.item_ttl = item_ttl; a.item_lock = const_cast<int64_t *>(item_lock); a.now = now;
+    a.entry_status = entry_status; a.result = result;
+    const hipError_t e = lzf_launch_store_mdel(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+uint64_t lzf_gpu_store_minc_work_size(uint32_t n)
+{
+    return lzf_minc_work_bytes(n);
+}
+
+int lzf_gpu_store_minc(const uint32_t *idx, uint32_t n, int64_t delta, int single,
+                       uint8_t *store, uint64_t store_cap, uint64_t *store_used,
+                       uint64_t *val_off, uint32_t *val_size, uint8_t *enc, uint32_t count,
+                       const int64_t *item_time, const int32_t *item_ttl, const int64_t *item_lock, int64_t now,
+                       int64_t *last_access, uint8_t *entry_status, int64_t *entry_value,
+                       uint64_t *result, uint32_t *status, void *work, void *stream)
+{
+    if (!idx || !store || !store_used || !val_off || !val_size || !enc || !result || !status || !work)
+        return LZF_GPU_EARG;
+    if (!n || !count || !item_time != !item_ttl || (item_lock && !item_time)) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfMincArgs a{};
+    a.idx = idx; a.n = n; a.delta = delta; a.single = single ? 1 : 0;
+    a.store = store; a.store_cap = store_cap; a.store_used = store_used;
+    a.val_off = val_off; a.val_size = val_size; a.enc = enc; a.count = count;
+    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
+    a.last_access = last_access; a.entry_status = entry_status; a.entry_value = entry_value;
+    a.result = result; a.status = status;
+    lzf_minc_carve(a, work);
+    const hipError_t e = lzf_launch_store_minc(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_host_parse_long(const uint8_t *v, uint32_t len, int64_t *out)
+{
+    if (!v || !out) return 0;
+    return lzf_ops_parse_long(v, len, out);
+}
+
+int lzf_gpu_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, uint8_t *enc, uint32_t count,
+                            const int64_t *item_time, const int64_t *item_lock, int64_t now,
+                            uint8_t *refused, uint64_t *result, void *stream)
+{
+    if (!occ || !enc || !item_time || !item_lock || !result) return LZF_GPU_EARG;
+    if (!count || !n || (uint64_t)first + n > count) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    const hipError_t e = lzf_launch_store_set_guard(occ, first, n, enc, count, item_time, item_lock, now, refused,
+                                                    result, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
 uint64_t lzf_gpu_key_index_bytes(uint32_t slots)
 {
     return lzf_kidx_slots_ok(slots) ? lzf_kidx_table_bytes(slots) : 0ull;

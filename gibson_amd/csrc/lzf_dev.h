@@ -2,12 +2,14 @@
  * lzf_dev.h -- device helpers shared by the compress kernels (lzf_cand.hip):
  * unaligned byte-window loads that never touch memory past a value's end,
  * and the reference's slot function; and the block-wide scan of the store's
- * kernels (lzf_store.hip, lzf_mget.hip).
+ * kernels (lzf_store.hip, lzf_mget.hip); and the per-item rules the index-list
+ * operators share (lzf_mget.hip, lzf_ops.hip): validity, lock, number parse.
  */
 #ifndef GIBSON_AMD_LZF_DEV_H
 #define GIBSON_AMD_LZF_DEV_H
 
 #include "lzf_internal.h"
+#include "../../include/lzf_gpu.h"
 
 __device__ __forceinline__ uint4 dv_ld16(const uint8_t *p)          /* unaligned */
 {
@@ -165,6 +167,61 @@ __device__ inline uint64_t dv_block_excl(uint64_t x, uint64_t *sw, uint64_t *tot
     __syncthreads();
     *total = all;
     return before + inc - x;
+}
+
+enum { MG_DEAD = 0, MG_EXPIRED = 1, MG_VALID = 2 };
+
+/* The validity rule of every index-list operator (gbIsItemStillValid,
+ * src/query.c:204-224, over the rule of src/query.c:186-189): entry i is dead
+ * when it is out of range or already NULL, expired when its ttl is positive
+ * and reached -- the caller then nulls enc[i], the device form of tr_remove --
+ * and valid otherwise.  No time arrays: nothing expires */
+__device__ inline int mg_validity(uint32_t i, uint32_t count, const uint8_t *enc, const int64_t *item_time,
+                                  const int32_t *item_ttl, int64_t now)
+{
+    if (i >= count || enc[i] == (uint8_t)LZF_ENC_NULL) return MG_DEAD;
+    if (item_ttl) {
+        const int32_t t = item_ttl[i];
+        /* now - time in two's complement, as the reference's time_t arithmetic wraps */
+        const int64_t age = (int64_t)((uint64_t)now - (uint64_t)item_time[i]);
+        if (t > 0 && age >= (int64_t)t) return MG_EXPIRED;
+    }
+    return MG_VALID;
+}
+
+/* The lock rule (gbItemIsLocked, src/query.c:171-178) for an in-range item i:
+ * locked for good at -1, otherwise while now - time is below the lock time.
+ * No lock array: nothing is locked */
+__device__ inline bool mg_locked(uint32_t i, const int64_t *item_time, const int64_t *item_lock, int64_t now)
+{
+    if (!item_lock) return false;
+    const int64_t lock = item_lock[i];
+    const int64_t age = (int64_t)((uint64_t)now - (uint64_t)item_time[i]);
+    return lock == -1 || age < lock;
+}
+
+/* gbQueryParseLong (src/query.c:39-76), quirk for quirk: a first byte '0'
+ * yields 0 whatever follows; a leading '-' negates and a lone "-" is 0; every
+ * other byte must be a digit; no length limit, the accumulation n * 10 + d and
+ * the negation modulo 2^64 (what the reference's x86-64 build computes where C
+ * leaves the signed overflow undefined).  len == 0: not a number (the
+ * reference asserts vlen > 0) */
+__host__ __device__ inline int lzf_parse_long(const uint8_t *v, uint32_t len, int64_t *out)
+{
+    if (!len) return 0;
+    if (v[0] == (uint8_t)'0') {
+        *out = 0;
+        return 1;
+    }
+    const uint32_t neg = v[0] == (uint8_t)'-' ? 1u : 0u;
+    uint64_t n = 0ull;
+    for (uint32_t i = neg; i < len; i++) {
+        const uint32_t d = (uint32_t)v[i] - (uint32_t)'0';
+        if (d > 9u) return 0;
+        n = n * 10ull + d;
+    }
+    *out = (int64_t)(neg ? 0ull - n : n);
+    return 1;
 }
 
 #endif

@@ -157,6 +157,54 @@ struct LzfKidxArgs {
     uint32_t *status;
 };
 
+/* the lock operators over an index list (lzf_ops.hip); device pointers.
+ * lock_time: MLOCK only; item_ttl / item_lock / last_access / entry_status
+ * may be NULL where the call allows it */
+struct LzfLockArgs {
+    const uint32_t *idx;
+    uint32_t n;
+    int64_t lock_time;
+    uint8_t *enc;
+    uint32_t count;
+    int64_t *item_time;
+    const int32_t *item_ttl;
+    int64_t *item_lock;
+    int64_t now;
+    int64_t *last_access;
+    uint8_t *entry_status;
+    uint64_t *result;
+};
+
+/* INC / DEC over an index list (lzf_ops.hip); device pointers */
+struct LzfMincArgs {
+    const uint32_t *idx;
+    uint32_t n;
+    int64_t delta;
+    int single;
+    uint8_t *store;
+    uint64_t store_cap;
+    uint64_t *store_used;
+    uint64_t *val_off;
+    uint32_t *val_size;
+    uint8_t *enc;
+    uint32_t count;
+    const int64_t *item_time;
+    const int32_t *item_ttl;
+    const int64_t *item_lock;
+    int64_t now;
+    int64_t *last_access;
+    uint8_t *entry_status;
+    int64_t *entry_value;
+    uint64_t *result;
+    uint32_t *status;
+    /* work area (lzf_minc_carve): the call's base and status; per entry its
+     * new number and its LZF_ENT_* class; per tile its converted entries, then
+     * the converted entries before it */
+    uint64_t *w_state, *w_tile;
+    int64_t *w_val;
+    uint8_t *w_cls;
+};
+
 /* compress scratch of the lane generation (lzf_lane.hip), device pointers:
  * per value cstride u16 cand words and bstride u32 inserted-bitmap words */
 struct LzfLaneScratch {
@@ -246,6 +294,19 @@ hipError_t lzf_launch_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc,
 hipError_t lzf_launch_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *enc, uint32_t count,
                                  int64_t *item_time, int32_t *item_ttl, int64_t now, int64_t *last_access,
                                  uint64_t *result, hipStream_t s);
+/* the lock-aware operators over an index list (lzf_ops.hip): MLOCK, MUNLOCK
+ * and MDEL in one pass each, INC / DEC in three launches, the SET guard over
+ * a lookup's output, and the number parse on the host */
+hipError_t lzf_launch_store_mlock(const LzfLockArgs &a, hipStream_t s);
+hipError_t lzf_launch_store_munlock(const LzfLockArgs &a, hipStream_t s);
+hipError_t lzf_launch_store_mdel(const LzfLockArgs &a, hipStream_t s);
+hipError_t lzf_launch_store_minc(LzfMincArgs &a, hipStream_t s);
+uint64_t lzf_minc_work_bytes(uint32_t n);
+void lzf_minc_carve(LzfMincArgs &a, void *work);
+hipError_t lzf_launch_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, uint8_t *enc, uint32_t count,
+                                      const int64_t *item_time, const int64_t *item_lock, int64_t now,
+                                      uint8_t *refused, uint64_t *result, hipStream_t s);
+int lzf_ops_parse_long(const uint8_t *v, uint32_t len, int64_t *out);
 /* the key index (lzf_kidx.hip): the table's geometry and a key's home slot on
  * the host, the upsert of the items [first, first + n) and the lookup of nq
  * query keys into idx */

@@ -1,7 +1,8 @@
 /*
  * lzf_mget.hip -- the operator layer over the device store: a prefix select
  * that yields an index list in HBM, and the index-list operators that need no
- * value arithmetic: MGET, COUNT and MTTL (include/lzf_gpu.h).
+ * value arithmetic: MGET, COUNT and MTTL (include/lzf_gpu.h).  INC / DEC and
+ * the lock operators are in lzf_ops.hip.
  *
  * Every multi-key operator of the reference is tr_search over a prefix plus a
  * callback per item found (src/query.c:526, 620, 687, 1171).  The callbacks of
@@ -68,25 +69,7 @@ namespace {
 /* state words of the mget work area */
 enum { MG_PAYLOAD = 0, MG_STATUS = 1, MG_FOUND = 2, MG_BAD = 3 };
 
-enum { MG_DEAD = 0, MG_EXPIRED = 1, MG_VALID = 2 };
-
-/* The validity rule of every index-list operator (gbIsItemStillValid,
- * src/query.c:204-224, over the rule of src/query.c:186-189): entry i is dead
- * when it is out of range or already NULL, expired when its ttl is positive
- * and reached -- the caller then nulls enc[i], the device form of tr_remove --
- * and valid otherwise.  No time arrays: nothing expires */
-__device__ inline int mg_validity(uint32_t i, uint32_t count, const uint8_t *enc, const int64_t *item_time,
-                                  const int32_t *item_ttl, int64_t now)
-{
-    if (i >= count || enc[i] == (uint8_t)LZF_ENC_NULL) return MG_DEAD;
-    if (item_ttl) {
-        const int32_t t = item_ttl[i];
-        /* now - time in two's complement, as the reference's time_t arithmetic wraps */
-        const int64_t age = (int64_t)((uint64_t)now - (uint64_t)item_time[i]);
-        if (t > 0 && age >= (int64_t)t) return MG_EXPIRED;
-    }
-    return MG_VALID;
-}
+/* mg_validity, the validity rule of every index-list operator: lzf_dev.h */
 
 /* ---- select ----------------------------------------------------------------- */
 

@@ -67,6 +67,13 @@ EXPORTS = (
     "lzf_host_key_home",
     "lzf_gpu_key_index_insert",
     "lzf_gpu_key_index_lookup",
+    "lzf_gpu_store_mlock",
+    "lzf_gpu_store_munlock",
+    "lzf_gpu_store_mdel",
+    "lzf_gpu_store_minc_work_size",
+    "lzf_gpu_store_minc",
+    "lzf_host_parse_long",
+    "lzf_gpu_store_set_guard",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -81,6 +88,8 @@ STORE_ERANGE = 3
 MGET_OK, MGET_NOT_FOUND, MGET_TOO_BIG, MGET_EDECODE = 0, 1, 2, 3
 # *status of key_index_insert (include/lzf_gpu.h)
 KIDX_OK, KIDX_FULL = 0, 1
+# entry_status of store_mlock / _munlock / _mdel / _minc (include/lzf_gpu.h)
+ENT_DONE, ENT_DEAD, ENT_EXPIRED, ENT_LOCKED, ENT_NAN, ENT_CONVERTED, ENT_UNCHANGED = 0, 1, 2, 3, 4, 5, 6
 
 # item encodings (src/net.h:274-278) and the MGET reply code (src/query.h:71)
 ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
@@ -194,6 +203,8 @@ def _load(path):
         _bind_store_index(L)
     if hasattr(L, "lzf_gpu_key_index_insert"):
         _bind_key_index(L)
+    if hasattr(L, "lzf_gpu_store_minc"):
+        _bind_store_ops(L)
     del i32
     _LOADED[path] = L
     return L
@@ -287,6 +298,28 @@ def _bind_key_index(L):
     L.lzf_gpu_key_index_insert.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
     L.lzf_gpu_key_index_lookup.restype = ctypes.c_int
     L.lzf_gpu_key_index_lookup.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp]
+
+
+def _bind_store_ops(L):
+    """Locks, the lock-aware DEL, INC / DEC and the SET guard of the device
+    store; absent from an older build given by LZF_HIP_LIB (the helpers below
+    then raise AttributeError)."""
+    u32, u64, vp, i64 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64
+    L.lzf_gpu_store_mlock.restype = ctypes.c_int
+    L.lzf_gpu_store_mlock.argtypes = [vp, u32, i64, vp, u32, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.lzf_gpu_store_munlock.restype = ctypes.c_int
+    L.lzf_gpu_store_munlock.argtypes = [vp, u32, vp, u32, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.lzf_gpu_store_mdel.restype = ctypes.c_int
+    L.lzf_gpu_store_mdel.argtypes = [vp, u32, vp, u32, vp, vp, vp, i64, vp, vp, vp]
+    L.lzf_gpu_store_minc_work_size.restype = u64
+    L.lzf_gpu_store_minc_work_size.argtypes = [u32]
+    L.lzf_gpu_store_minc.restype = ctypes.c_int
+    L.lzf_gpu_store_minc.argtypes = [vp, u32, i64, ctypes.c_int, vp, u64, vp, vp, vp, vp, u32, vp, vp, vp, i64, vp,
+                                     vp, vp, vp, vp, vp, vp]
+    L.lzf_host_parse_long.restype = ctypes.c_int
+    L.lzf_host_parse_long.argtypes = [vp, u32, vp]
+    L.lzf_gpu_store_set_guard.restype = ctypes.c_int
+    L.lzf_gpu_store_set_guard.argtypes = [vp, u32, u32, vp, u32, vp, vp, i64, vp, vp, vp]
 
 
 def selfcheck():
@@ -743,6 +776,97 @@ def key_index_lookup(table, keys, key_off, key_len, enc, qkeys, q_off, q_len, id
                                         _ptr(enc), int(enc.numel()), _ptr(qkeys), _ptr(q_off), _ptr(q_len),
                                         int(q_len.numel()), _ptr(idx), _ptr(result), _stream_handle(stream))
     _check(rc, "lzf_gpu_key_index_lookup")
+
+
+# ---- locks, the lock-aware DEL, INC / DEC over an index list --------------------
+
+def store_mlock(idx, lock_time, enc, item_time, item_ttl, item_lock, now, result, last_access=None,
+                entry_status=None, stream=None):
+    """LOCK / MLOCK over an index list of distinct entries: an entry that is
+    valid and not locked (item_lock == -1, or now - item_time < item_lock)
+    gets item_time = last_access = now and item_lock = lock_time; an expired
+    one becomes ENC_NULL.  item_time / item_lock int64, item_ttl int32;
+    entry_status (uint8, one ENT_* per entry) is optional; result (3 elements,
+    int64) = locked by this call, expired, refused as locked.  No host wait."""
+    _check(lib().lzf_gpu_store_mlock(_ptr(idx), int(idx.numel()), int(lock_time), _ptr(enc), int(enc.numel()),
+                                     _ptr(item_time), _ptr(item_ttl), _ptr(item_lock), int(now),
+                                     _opt_ptr(last_access), _opt_ptr(entry_status), _ptr(result),
+                                     _stream_handle(stream)), "lzf_gpu_store_mlock")
+
+
+def store_munlock(idx, enc, item_time, item_ttl, item_lock, now, result, last_access=None, entry_status=None,
+                  stream=None):
+    """UNLOCK / MUNLOCK over an index list: a valid entry gets item_lock = 0
+    and last_access = now, locked or not; result (2 elements, int64) = found,
+    expired.  No host wait."""
+    _check(lib().lzf_gpu_store_munlock(_ptr(idx), int(idx.numel()), _ptr(enc), int(enc.numel()), _ptr(item_time),
+                                       _ptr(item_ttl), _ptr(item_lock), int(now), _opt_ptr(last_access),
+                                       _opt_ptr(entry_status), _ptr(result), _stream_handle(stream)),
+           "lzf_gpu_store_munlock")
+
+
+def store_mdel(idx, enc, item_time, item_ttl, item_lock, now, result, entry_status=None, stream=None):
+    """The lock-aware DEL / MDEL over an index list, in one launch: a locked
+    entry is left alone (the lock is tested first, on an expired item too), an
+    expired one becomes ENC_NULL uncounted, a valid one becomes ENC_NULL.
+    item_time / item_ttl may both be None, item_lock may be None; result (3
+    elements, int64) = deleted, expired, locked.  No host wait."""
+    _check(lib().lzf_gpu_store_mdel(_ptr(idx), int(idx.numel()), _ptr(enc), int(enc.numel()), _opt_ptr(item_time),
+                                    _opt_ptr(item_ttl), _opt_ptr(item_lock), int(now), _opt_ptr(entry_status),
+                                    _ptr(result), _stream_handle(stream)), "lzf_gpu_store_mdel")
+
+
+def store_minc_work(n, device):
+    """A scratch tensor for one store_minc call over a list of ``n`` entries."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_minc_work_size(int(n))), dtype=torch.uint8, device=device)
+
+
+def store_minc(idx, delta, store, store_used, val_off, val_size, enc, item_time, item_ttl, item_lock, now, result,
+               status, single=False, last_access=None, entry_status=None, entry_value=None, work=None, stream=None):
+    """INC / DEC / MINC / MDEC over an index list of distinct entries: a NUMBER
+    item's 8 stored bytes become value + delta; a PLAIN item whose bytes parse
+    (parse_long) becomes a NUMBER item in a fresh 8-byte slot appended to
+    ``store`` in list order from ``store_used[0]`` on, which is advanced; an
+    LZF item is counted and left (``single``: not a number).  Locked entries
+    are left alone, expired ones become ENC_NULL.  The cap is the store
+    tensor's length.  item_time / item_ttl may both be None, item_lock may be
+    None.  result (6 elements, int64) = found, expired, locked, nan,
+    converted, unchanged; status (1 element, int32) = STORE_OK, or STORE_FULL
+    with nothing changed and result zero; entry_status (uint8) and entry_value
+    (int64, the new numbers) are optional.  No host wait; returns ``work``
+    (store_minc_work), which must outlive the stream's work."""
+    n = idx.numel()
+    if work is None:
+        work = store_minc_work(n, store.device)
+    rc = lib().lzf_gpu_store_minc(_ptr(idx), n, int(delta), 1 if single else 0, _ptr(store), int(store.numel()),
+                                  _ptr(store_used), _ptr(val_off), _ptr(val_size), _ptr(enc), int(enc.numel()),
+                                  _opt_ptr(item_time), _opt_ptr(item_ttl), _opt_ptr(item_lock), int(now),
+                                  _opt_ptr(last_access), _opt_ptr(entry_status), _opt_ptr(entry_value), _ptr(result),
+                                  _ptr(status), _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_minc")
+    return work
+
+
+def parse_long(value):
+    """lzf_host_parse_long(): gbQueryParseLong (src/query.c:39-76) over a bytes
+    value -- the number, or None when the value is not one.  No GPU."""
+    value = bytes(value)
+    out = ctypes.c_int64(0)
+    ok = lib().lzf_host_parse_long(ctypes.c_char_p(value), len(value), ctypes.byref(out))
+    return int(out.value) if ok else None
+
+
+def store_set_guard(occ, first, enc, item_time, item_lock, now, result, refused=None, stream=None):
+    """SET on a locked key, between key_index_lookup of a batch's own keys
+    (``occ``, int32 read as u32, one entry per new item from ``first`` on) and
+    its key_index_insert: a new item whose key is held by a live, locked item
+    outside the batch becomes ENC_NULL, so the insert skips it.  refused
+    (uint8, optional) = 1 per refused item; result (1 element, int64) = how
+    many.  No host wait."""
+    _check(lib().lzf_gpu_store_set_guard(_ptr(occ), int(first), int(occ.numel()), _ptr(enc), int(enc.numel()),
+                                         _ptr(item_time), _ptr(item_lock), int(now), _opt_ptr(refused), _ptr(result),
+                                         _stream_handle(stream)), "lzf_gpu_store_set_guard")
 
 
 def host_register(arr):

@@ -541,6 +541,156 @@ int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *en
                        int64_t *last_access, uint64_t *result /* 2 u64: changed, expired */, void *stream);
 
 /*
+ * Locks, the lock-aware DEL and INC / DEC over an index list.
+ *
+ * The store has one more caller-owned per-item array, item_lock (i64[count],
+ * the reference's time_t lock, src/net.h:295), which the caller zeroes for new
+ * items as it owns item_time and item_ttl.  The lock rule (gbItemIsLocked,
+ * src/query.c:171-178): item i is locked iff
+ *   item_lock[i] == -1 || now - item_time[i] < item_lock[i]
+ * with the subtraction in two's complement, as in the validity rule above.
+ * The operators below are the callbacks of LOCK / MLOCK, UNLOCK / MUNLOCK,
+ * DEL / MDEL and INC / DEC / MINC / MDEC applied to an index list; with
+ * MGET, COUNT and MTTL they are the reference's operator table over the
+ * device store.  Every pointer is device memory, every call validates its
+ * arguments before any HIP call (LZF_GPU_EARG: a NULL pointer but the
+ * optional ones, n == 0, count == 0, and what each call names), is
+ * asynchronous on `stream` and waits for nothing on the host.  count and n:
+ * up to 2^32 - 1, all byte arithmetic 64-bit.  An idx entry >= count is
+ * ignored.  Nothing outside the sizes named is written.
+ *
+ * entry_status (n device bytes, optional: NULL is not written) receives one
+ * LZF_ENT_* code per entry; the host derives the single-key replies from
+ * entry 0 (REPL_OK, REPL_ERR_NOT_FOUND, REPL_ERR_LOCKED, REPL_ERR_NAN).
+ * Entries should be distinct, as a select or a lookup of distinct keys yields
+ * them; a duplicate is memory-safe, its counts and values unspecified.
+ */
+#define LZF_ENT_DONE       0   /* the operator applied */
+#define LZF_ENT_DEAD       1   /* out of range, padding, or already LZF_ENC_NULL */
+#define LZF_ENT_EXPIRED    2   /* expired: this call set enc[i] = LZF_ENC_NULL */
+#define LZF_ENT_LOCKED     3   /* locked: untouched */
+#define LZF_ENT_NAN        4   /* minc: the value is not a number */
+#define LZF_ENT_CONVERTED  5   /* minc: a PLAIN item became a NUMBER item */
+#define LZF_ENT_UNCHANGED  6   /* minc: an LZF item, counted but untouched */
+
+/* LOCK / MLOCK, gbMultiLockCallback (src/query.c:1015-1036).  Per entry, in
+ * this order: dead -> DEAD; expired -> EXPIRED and nulled; locked -> LOCKED,
+ * nothing written; otherwise item_time[i] = last_access[i] = now and
+ * item_lock[i] = lock_time -> DONE.  Writing item_time restarts the item's TTL
+ * clock, as in the reference.  item_time, item_ttl and item_lock are required.
+ * result (3 device u64): [0] locked by this call (the reply of
+ * gbQueryMultiLockHandler), [1] expired, [2] refused as locked. */
+int lzf_gpu_store_mlock(const uint32_t *idx, uint32_t n, int64_t lock_time, uint8_t *enc, uint32_t count,
+                        int64_t *item_time, const int32_t *item_ttl, int64_t *item_lock, int64_t now,
+                        int64_t *last_access /* may be NULL */, uint8_t *entry_status /* may be NULL */,
+                        uint64_t *result /* 3 u64: locked now, expired, refused */, void *stream);
+/* UNLOCK / MUNLOCK, gbMultiUnlockCallback (src/query.c:1097-1114): a valid
+ * entry gets item_lock[i] = 0 and last_access[i] = now, locked or not ->
+ * DONE; dead and expired entries as above.  item_time is read only.  result
+ * (2 device u64): [0] found, [1] expired. */
+int lzf_gpu_store_munlock(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
+                          const int64_t *item_time, const int32_t *item_ttl, int64_t *item_lock, int64_t now,
+                          int64_t *last_access /* may be NULL */, uint8_t *entry_status /* may be NULL */,
+                          uint64_t *result /* 2 u64: found, expired */, void *stream);
+/* The lock-aware DEL / MDEL, gbMultiDelCallback (src/query.c:778-800), the
+ * one-launch form of lzf_gpu_store_count followed by lzf_gpu_store_delete for
+ * a store that uses locks.  Per entry, in this order: dead -> DEAD; locked --
+ * tested first, on an expired item too (:789) -> LOCKED, untouched; expired
+ * -> EXPIRED, nulled, not counted; valid -> enc[i] = LZF_ENC_NULL, DONE.
+ * last_access is not written.  item_time and item_ttl: both NULL (nothing
+ * expires) or both given; item_lock may be NULL (nothing is locked) and needs
+ * item_time otherwise.  result (3 device u64): [0] deleted (the reply of
+ * gbQueryMultiDelHandler), [1] expired, [2] locked. */
+int lzf_gpu_store_mdel(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
+                       const int64_t *item_time, const int32_t *item_ttl, const int64_t *item_lock /* may be NULL */,
+                       int64_t now, uint8_t *entry_status /* may be NULL */,
+                       uint64_t *result /* 3 u64: deleted, expired, locked */, void *stream);
+
+/*
+ * INC / DEC / MINC / MDEC: value + delta for every entry of the list.
+ *
+ * single == 0, gbMultiIncDecCallback (src/query.c:898-940), per entry in this
+ * order: dead -> DEAD; locked -> LOCKED, untouched; expired -> EXPIRED,
+ * nulled.  A valid entry gets last_access[i] = now -- before the value test,
+ * so a NAN entry gets it too -- and then, by its encoding:
+ *   LZF_ENC_NUMBER  the 8 stored little-endian bytes at store + val_off[i]
+ *                   become value + delta                      -> DONE;
+ *   LZF_ENC_PLAIN   whose bytes parse by the rule below: the item becomes a
+ *                   NUMBER item holding parsed + delta        -> CONVERTED;
+ *                   that do not parse, or of size 0           -> NAN, unchanged
+ *                   and not counted;
+ *   anything else   (LZF) -> UNCHANGED, and counted as found: the callback
+ *                   falls through to return 1 (:939).
+ * single != 0, gbQueryIncDecHandler (src/query.c:853-886): validity is tested
+ * before the lock, so a locked and expired entry is EXPIRED and nulled, and an
+ * LZF item is NAN.  Creating the item of a missing key (:842-851) is not
+ * modelled: the entry reports DEAD and the host SETs 1.
+ *
+ * The parse rule (gbQueryParseLong, src/query.c:39-76): a first byte '0'
+ * yields 0 whatever follows; a leading '-' negates, and a lone "-" yields 0;
+ * every remaining byte must be '0'..'9' ("+5" and " 5" are not numbers);
+ * there is no length limit, n = n * 10 + d accumulates modulo 2^64 -- what
+ * the reference's x86-64 build computes where C leaves signed overflow
+ * undefined -- and + delta wraps the same way.  lzf_host_parse_long is the
+ * same rule on the host, with no HIP call: 1 and *out, or 0 (len == 0 and a
+ * NULL pointer included).  One lane walks an entry's value serially: a
+ * megabyte of digits costs one lane a megabyte of reads.
+ *
+ * A converted number gets a fresh 8-byte slot appended to the arena in list
+ * order: for the k-th entry, val_off[i] = base + 8 * (CONVERTED entries
+ * before k) with base = *store_used, val_size[i] = 8, enc[i] =
+ * LZF_ENC_NUMBER, and *store_used = base + 8 * converted.  The old PLAIN
+ * bytes become dead space, which lzf_gpu_store_compact reclaims.  Offsets are
+ * dense and not 8-aligned: numbers are read and written at any alignment.
+ *
+ * *status (one device u32): LZF_STORE_OK, or LZF_STORE_FULL when base + 8 *
+ * converted > store_cap or the sum wraps.  Then nothing changes -- not store,
+ * val_off, val_size, enc, last_access, *store_used, entry_status or
+ * entry_value -- and result is all zero.
+ *
+ * A NUMBER item whose val_size != 8 or whose [val_off, val_off + 8) leaves
+ * [0, store_cap), and a PLAIN item whose [val_off, val_off + val_size) does,
+ * is NAN and is not dereferenced.
+ *
+ * item_lock == NULL: nothing is locked; item_time and item_ttl: both NULL
+ * (nothing expires) or both given; a non-NULL item_lock needs item_time.
+ * result (6 device u64): [0] found = DONE + CONVERTED + UNCHANGED (the reply
+ * of gbQueryMultiIncDecHandler), [1] expired, [2] locked, [3] nan,
+ * [4] converted, [5] unchanged.  entry_value (n device i64, optional): the new
+ * number for DONE and CONVERTED, the payload of the single-key REPL_VAL reply,
+ * 0 otherwise.  work: lzf_gpu_store_minc_work_size(n) bytes of device scratch
+ * that must stay valid until the stream's work is done.
+ */
+uint64_t lzf_gpu_store_minc_work_size(uint32_t n);
+int lzf_gpu_store_minc(const uint32_t *idx, uint32_t n, int64_t delta, int single,
+                       uint8_t *store, uint64_t store_cap, uint64_t *store_used,
+                       uint64_t *val_off, uint32_t *val_size, uint8_t *enc, uint32_t count,
+                       const int64_t *item_time, const int32_t *item_ttl,
+                       const int64_t *item_lock /* may be NULL */, int64_t now,
+                       int64_t *last_access /* may be NULL */,
+                       uint8_t *entry_status /* may be NULL */, int64_t *entry_value /* may be NULL, n */,
+                       uint64_t *result /* 6 u64 */, uint32_t *status, void *work, void *stream);
+int lzf_host_parse_long(const uint8_t *v, uint32_t len, int64_t *out);
+
+/*
+ * SET on a locked key (src/query.c:446-451).  Runs between a
+ * lzf_gpu_key_index_lookup of the new items' own keys -- occ[n], the lookup's
+ * output for the items [first, first + n) -- and their
+ * lzf_gpu_key_index_insert.  Per k, with j = occ[k]: if j < count, j lies
+ * outside [first, first + n), enc[j] != LZF_ENC_NULL and item j is locked,
+ * then enc[first + k] = LZF_ENC_NULL, refused[k] = 1 and result[0] grows by
+ * one; otherwise refused[k] = 0.  The reference tests no validity here, so
+ * neither does this.  The insert then skips the new item, its stored bytes are
+ * dead space, and the old item stays the key's mapping.  refused (n device
+ * bytes) may be NULL; result: 1 device u64.  LZF_GPU_EARG also for
+ * first + n > count.  So set_store -> lookup -> set_guard -> insert queues on
+ * one stream, and the host reads `refused` back with the reply.
+ */
+int lzf_gpu_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, uint8_t *enc, uint32_t count,
+                            const int64_t *item_time, const int64_t *item_lock, int64_t now,
+                            uint8_t *refused /* may be NULL */, uint64_t *result /* 1 u64 */, void *stream);
+
+/*
  * The device key index: exact-key lookup and upsert for the device store.
  *
  * The operators above address items by index.  The key index maps key bytes
@@ -571,8 +721,9 @@ int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *en
  * with lzf_gpu_store_compact: both are the store's housekeeping, run when
  * lzf_gpu_store_usage shows enough dead items, and item indices survive both.
  *
- * Not modelled: locks -- SET on a locked item replies REPL_ERR_LOCKED
- * (src/query.c:446-451) and the host still decides that; the single-item GET
+ * Locks: SET on a locked item replies REPL_ERR_LOCKED (src/query.c:446-451);
+ * lzf_gpu_store_set_guard, run between the lookup of a batch's own keys and
+ * its insert, decides that on the device.  Not modelled: the single-item GET
  * reply (gbClientEnqueueItem) -- the lookup yields the index, and the KVAL
  * frame of lzf_gpu_store_mget is what the device writes; the ordered prefix
  * walk, which stays with the host's trie.
