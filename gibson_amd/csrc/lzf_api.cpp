@@ -1056,6 +1056,96 @@ int lzf_gpu_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, uin
     return e == hipSuccess ? LZF_GPU_OK : code_of(e);
 }
 
+uint64_t lzf_gpu_store_mset_work_size(uint32_t n, uint32_t vlen)
+{
+    return lzf_mset_work_bytes(n, vlen);
+}
+
+int lzf_gpu_store_mset(const uint32_t *idx, uint32_t n, const uint8_t *value, uint32_t vlen, uint32_t compression,
+                       uint8_t *store, uint64_t store_cap, uint64_t *store_used,
+                       uint64_t *val_off, uint32_t *val_size, uint8_t *enc, uint32_t *val_len, uint32_t count,
+                       int64_t *item_time, int32_t *item_ttl, int64_t *item_lock, int64_t now,
+                       int64_t *last_access, uint8_t *entry_status, uint64_t *result, uint32_t *status,
+                       void *work, void *stream)
+{
+    if (!idx || !value || !store || !store_used || !val_off || !val_size || !enc || !val_len || !item_time ||
+        !item_ttl || !result || !status || !work)
+        return LZF_GPU_EARG;
+    if (!n || !count || !store_cap) return LZF_GPU_EARG;
+    if (!vlen || vlen > LZF_GPU_MAX_VALUE) return LZF_GPU_EARG;   /* the reference asserts vlen > 0 */
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfMsetArgs a{};
+    a.idx = idx; a.n = n; a.value = value; a.vlen = vlen; a.compression = compression;
+    a.store = store; a.store_cap = store_cap; a.store_used = store_used;
+    a.val_off = val_off; a.val_size = val_size; a.enc = enc; a.val_len = val_len; a.count = count;
+    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
+    a.last_access = last_access; a.entry_status = entry_status; a.result = result; a.status = status;
+    lzf_mset_carve(a, work);
+    const hipError_t e = lzf_launch_store_mset(a, (hipStream_t)stream, store_compress);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_gpu_store_gc(const int64_t *last_access, int64_t now, int64_t gc_ratio,
+                     uint8_t *enc, const uint32_t *val_size, uint32_t count,
+                     const uint64_t *gate, uint64_t max_bytes, uint64_t *result, void *stream)
+{
+    if (!last_access || !enc || !val_size || !result || !count) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    const hipError_t e = lzf_launch_store_gc(last_access, now, gc_ratio, enc, val_size, count, gate, max_bytes,
+                                             result, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_host_meta_field(const uint8_t *m, uint32_t mlen)
+{
+    return lzf_meta_field(m, mlen);
+}
+
+int lzf_gpu_store_meta(const uint32_t *idx, uint32_t n, int field, uint8_t *enc, const uint32_t *val_size,
+                       uint32_t count, const int64_t *item_time, const int32_t *item_ttl,
+                       const int64_t *item_lock, int64_t now, int64_t *last_access,
+                       uint8_t *entry_status, int64_t *entry_value, uint64_t *result, void *stream)
+{
+    if (!idx || !enc || !val_size || !item_time || !item_ttl || !entry_value || !result) return LZF_GPU_EARG;
+    if (!n || !count || field < LZF_META_SIZE || field > LZF_META_LOCK) return LZF_GPU_EARG;
+    if (field == LZF_META_ACCESS && !last_access) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfMetaArgs a{};
+    a.idx = idx; a.n = n; a.field = field; a.enc = enc; a.val_size = val_size; a.count = count;
+    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
+    a.last_access = last_access; a.entry_status = entry_status; a.entry_value = entry_value; a.result = result;
+    const hipError_t e = lzf_launch_store_meta(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+uint64_t lzf_gpu_store_keys_work_size(uint32_t n)
+{
+    return lzf_keys_work_bytes(n);
+}
+
+int lzf_gpu_store_keys(const uint32_t *idx, uint32_t n,
+                       const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                       const uint8_t *enc, uint32_t count, int reply_header,
+                       uint8_t *frame, uint64_t max_response, uint64_t *frame_len,
+                       uint64_t *result, void *work, void *stream)
+{
+    if (!idx || !keys || !key_off || !key_len || !enc || !frame || !frame_len || !result || !work)
+        return LZF_GPU_EARG;
+    if (!n || !count) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    LzfKeysArgs a{};
+    a.idx = idx; a.n = n; a.keys = keys; a.key_off = key_off; a.key_len = key_len; a.enc = enc; a.count = count;
+    a.reply_header = reply_header;
+    a.frame = frame; a.max_response = max_response; a.frame_len = frame_len; a.result = result;
+    lzf_keys_carve(a, work);
+    const hipError_t e = lzf_launch_store_keys(a, (hipStream_t)stream);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
 uint64_t lzf_gpu_key_index_bytes(uint32_t slots)
 {
     return lzf_kidx_slots_ok(slots) ? lzf_kidx_table_bytes(slots) : 0ull;

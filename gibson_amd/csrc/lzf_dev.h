@@ -2,8 +2,10 @@
  * lzf_dev.h -- device helpers shared by the compress kernels (lzf_cand.hip):
  * unaligned byte-window loads that never touch memory past a value's end,
  * and the reference's slot function; and the block-wide scan of the store's
- * kernels (lzf_store.hip, lzf_mget.hip); and the per-item rules the index-list
- * operators share (lzf_mget.hip, lzf_ops.hip): validity, lock, number parse.
+ * kernels (lzf_store.hip, lzf_mget.hip) with the carry scan over tile sums
+ * (lzf_mset.hip, lzf_meta.hip); and the per-item rules the index-list
+ * operators share (lzf_mget.hip, lzf_ops.hip, lzf_mset.hip, lzf_meta.hip):
+ * validity, lock, number parse.
  */
 #ifndef GIBSON_AMD_LZF_DEV_H
 #define GIBSON_AMD_LZF_DEV_H
@@ -167,6 +169,35 @@ __device__ inline uint64_t dv_block_excl(uint64_t x, uint64_t *sw, uint64_t *tot
     __syncthreads();
     *total = all;
     return before + inc - x;
+}
+
+/* one workgroup of WAVES waves: the exclusive scan of the n sums at v in place,
+ * in pieces of 64 * WAVES * DV_CARRY_PER with a running carry, a thread taking
+ * DV_CARRY_PER neighbouring sums (the carry step between a per-tile reduce and
+ * a per-tile write, lzf_mset.hip, lzf_meta.hip); the total, in every thread */
+#define DV_CARRY_PER 8u
+template <uint32_t WAVES>
+__device__ inline uint64_t dv_carry_scan(uint64_t *v, uint32_t n, uint64_t *sw)
+{
+    uint64_t run = 0ull;
+    for (uint64_t c = 0; c < n; c += 64u * WAVES * DV_CARRY_PER) {
+        const uint64_t first = c + threadIdx.x * DV_CARRY_PER;
+        uint64_t x[DV_CARRY_PER], s = 0ull;
+#pragma unroll
+        for (uint32_t j = 0; j < DV_CARRY_PER; j++) {
+            x[j] = first + j < n ? v[first + j] : 0ull;
+            s += x[j];
+        }
+        uint64_t tot;
+        uint64_t o = run + dv_block_excl<WAVES>(s, sw, &tot);
+#pragma unroll
+        for (uint32_t j = 0; j < DV_CARRY_PER; j++) {
+            if (first + j < n) v[first + j] = o;
+            o += x[j];
+        }
+        run += tot;
+    }
+    return run;
 }
 
 enum { MG_DEAD = 0, MG_EXPIRED = 1, MG_VALID = 2 };

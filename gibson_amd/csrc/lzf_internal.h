@@ -205,6 +205,74 @@ struct LzfMincArgs {
     uint8_t *w_cls;
 };
 
+/* MSET over an index list (lzf_mset.hip); device pointers */
+struct LzfMsetArgs {
+    const uint32_t *idx;
+    uint32_t n;
+    const uint8_t *value;
+    uint32_t vlen, compression;
+    uint8_t *store;
+    uint64_t store_cap;
+    uint64_t *store_used;
+    uint64_t *val_off;
+    uint32_t *val_size;
+    uint8_t *enc;
+    uint32_t *val_len;
+    uint32_t count;
+    int64_t *item_time;
+    int32_t *item_ttl;
+    int64_t *item_lock;
+    int64_t now;
+    int64_t *last_access;
+    uint8_t *entry_status;
+    uint64_t *result;
+    uint32_t *status;
+    /* work area (lzf_mset_carve): the call's base, status and stored form; the
+     * descriptors of the one-value compress batch (c_off: in_off, out_off;
+     * c_len: in_len, out_cap, out_len); per tile its DONE entries, then the
+     * DONE entries before it; per entry its LZF_ENT_* class; the compress slot */
+    uint64_t *w_state, *c_off, *w_tile;
+    uint32_t *c_len;
+    uint8_t *w_cls, *w_slot;
+};
+
+/* META over an index list (lzf_meta.hip); device pointers */
+struct LzfMetaArgs {
+    const uint32_t *idx;
+    uint32_t n;
+    int field;
+    uint8_t *enc;
+    const uint32_t *val_size;
+    uint32_t count;
+    const int64_t *item_time;
+    const int32_t *item_ttl;
+    const int64_t *item_lock;
+    int64_t now;
+    int64_t *last_access;
+    uint8_t *entry_status;
+    int64_t *entry_value;
+    uint64_t *result;
+};
+
+/* the KEYS reply frame over an index list (lzf_meta.hip); device pointers */
+struct LzfKeysArgs {
+    const uint32_t *idx;
+    uint32_t n;
+    const uint8_t *keys;
+    const uint64_t *key_off;
+    const uint32_t *key_len;
+    const uint8_t *enc;
+    uint32_t count;
+    int reply_header;
+    uint8_t *frame;
+    uint64_t max_response;
+    uint64_t *frame_len;
+    uint64_t *result;
+    /* work area (lzf_keys_carve): found, payload, status; per tile its
+     * participating entries and their key bytes, then those before it */
+    uint64_t *w_state, *w_tile_n, *w_tile_b;
+};
+
 /* compress scratch of the lane generation (lzf_lane.hip), device pointers:
  * per value cstride u16 cand words and bstride u32 inserted-bitmap words */
 struct LzfLaneScratch {
@@ -307,6 +375,22 @@ hipError_t lzf_launch_store_set_guard(const uint32_t *occ, uint32_t first, uint3
                                       const int64_t *item_time, const int64_t *item_lock, int64_t now,
                                       uint8_t *refused, uint64_t *result, hipStream_t s);
 int lzf_ops_parse_long(const uint8_t *v, uint32_t len, int64_t *out);
+/* MSET over an index list (lzf_mset.hip): classify, `compress` over the one
+ * value, the decision, the descriptors, the replicated stored bytes */
+hipError_t lzf_launch_store_mset(LzfMsetArgs &a, hipStream_t s,
+                                 hipError_t (*compress)(const LzfBatch &, hipStream_t));
+uint64_t lzf_mset_work_bytes(uint32_t n, uint32_t vlen);
+void lzf_mset_carve(LzfMsetArgs &a, void *work);
+/* the memory sweep, META and the KEYS frame (lzf_meta.hip), and META's field
+ * name on the host */
+hipError_t lzf_launch_store_gc(const int64_t *last_access, int64_t now, int64_t gc_ratio, uint8_t *enc,
+                               const uint32_t *val_size, uint32_t count, const uint64_t *gate, uint64_t max_bytes,
+                               uint64_t *result, hipStream_t s);
+hipError_t lzf_launch_store_meta(const LzfMetaArgs &a, hipStream_t s);
+int lzf_meta_field(const uint8_t *m, uint32_t mlen);
+hipError_t lzf_launch_store_keys(LzfKeysArgs &a, hipStream_t s);
+uint64_t lzf_keys_work_bytes(uint32_t n);
+void lzf_keys_carve(LzfKeysArgs &a, void *work);
 /* the key index (lzf_kidx.hip): the table's geometry and a key's home slot on
  * the host, the upsert of the items [first, first + n) and the lookup of nq
  * query keys into idx */

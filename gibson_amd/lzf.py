@@ -74,6 +74,13 @@ EXPORTS = (
     "lzf_gpu_store_minc",
     "lzf_host_parse_long",
     "lzf_gpu_store_set_guard",
+    "lzf_gpu_store_mset_work_size",
+    "lzf_gpu_store_mset",
+    "lzf_gpu_store_gc",
+    "lzf_host_meta_field",
+    "lzf_gpu_store_meta",
+    "lzf_gpu_store_keys_work_size",
+    "lzf_gpu_store_keys",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -90,6 +97,8 @@ MGET_OK, MGET_NOT_FOUND, MGET_TOO_BIG, MGET_EDECODE = 0, 1, 2, 3
 KIDX_OK, KIDX_FULL = 0, 1
 # entry_status of store_mlock / _munlock / _mdel / _minc (include/lzf_gpu.h)
 ENT_DONE, ENT_DEAD, ENT_EXPIRED, ENT_LOCKED, ENT_NAN, ENT_CONVERTED, ENT_UNCHANGED = 0, 1, 2, 3, 4, 5, 6
+# field of store_meta, as meta_field resolves a name (include/lzf_gpu.h)
+META_SIZE, META_ENCODING, META_ACCESS, META_CREATED, META_TTL, META_LEFT, META_LOCK = 0, 1, 2, 3, 4, 5, 6
 
 # item encodings (src/net.h:274-278) and the MGET reply code (src/query.h:71)
 ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
@@ -205,6 +214,8 @@ def _load(path):
         _bind_key_index(L)
     if hasattr(L, "lzf_gpu_store_minc"):
         _bind_store_ops(L)
+    if hasattr(L, "lzf_gpu_store_mset"):
+        _bind_store_mset(L)
     del i32
     _LOADED[path] = L
     return L
@@ -320,6 +331,28 @@ def _bind_store_ops(L):
     L.lzf_host_parse_long.argtypes = [vp, u32, vp]
     L.lzf_gpu_store_set_guard.restype = ctypes.c_int
     L.lzf_gpu_store_set_guard.argtypes = [vp, u32, u32, vp, u32, vp, vp, i64, vp, vp, vp]
+
+
+def _bind_store_mset(L):
+    """MSET by prefix, the memory sweep, META and the KEYS frame of the device
+    store; absent from an older build given by LZF_HIP_LIB (the helpers below
+    then raise AttributeError)."""
+    u32, u64, vp, i64 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64
+    L.lzf_gpu_store_mset_work_size.restype = u64
+    L.lzf_gpu_store_mset_work_size.argtypes = [u32, u32]
+    L.lzf_gpu_store_mset.restype = ctypes.c_int
+    L.lzf_gpu_store_mset.argtypes = [vp, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp, u32, vp, vp, vp, i64, vp, vp,
+                                     vp, vp, vp, vp]
+    L.lzf_gpu_store_gc.restype = ctypes.c_int
+    L.lzf_gpu_store_gc.argtypes = [vp, i64, i64, vp, vp, u32, vp, u64, vp, vp]
+    L.lzf_host_meta_field.restype = ctypes.c_int
+    L.lzf_host_meta_field.argtypes = [vp, u32]
+    L.lzf_gpu_store_meta.restype = ctypes.c_int
+    L.lzf_gpu_store_meta.argtypes = [vp, u32, ctypes.c_int, vp, vp, u32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.lzf_gpu_store_keys_work_size.restype = u64
+    L.lzf_gpu_store_keys_work_size.argtypes = [u32]
+    L.lzf_gpu_store_keys.restype = ctypes.c_int
+    L.lzf_gpu_store_keys.argtypes = [vp, u32, vp, vp, vp, vp, u32, ctypes.c_int, vp, u64, vp, vp, vp, vp]
 
 
 def selfcheck():
@@ -867,6 +900,103 @@ def store_set_guard(occ, first, enc, item_time, item_lock, now, result, refused=
     _check(lib().lzf_gpu_store_set_guard(_ptr(occ), int(first), int(occ.numel()), _ptr(enc), int(enc.numel()),
                                          _ptr(item_time), _ptr(item_lock), int(now), _opt_ptr(refused), _ptr(result),
                                          _stream_handle(stream)), "lzf_gpu_store_set_guard")
+
+
+# ---- MSET by prefix, the memory sweep, META and the KEYS frame --------------------
+
+def store_mset_work(n, vlen, device):
+    """A scratch tensor for one store_mset call of a ``vlen``-byte value over a
+    list of ``n`` entries."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_mset_work_size(int(n), int(vlen))), dtype=torch.uint8, device=device)
+
+
+def store_mset(idx, value, compression, store, store_used, val_off, val_size, enc, val_len, item_time, item_ttl,
+               item_lock, now, result, status, last_access=None, entry_status=None, work=None, stream=None):
+    """MSET over an index list of distinct entries: every entry that is valid
+    and not locked (the lock is tested first, on an expired item too) gets the
+    new ``value`` (a uint8 tensor on the device, at least one byte).  Its
+    stored form is decided once, as set_store decides it for that one value --
+    compressed iff its length > ``compression``, kept LZF iff a stream of at
+    most length - 4 bytes exists -- and every such entry gets its own copy,
+    appended to ``store`` in list order from ``store_used[0]`` on, which is
+    advanced; val_off, val_size, enc and val_len are rewritten, item_time =
+    last_access = now, item_ttl = -1, item_lock = 0.  Expired entries become
+    ENC_NULL.  The cap is the store tensor's length; ``value`` must not lie in
+    the store's free part.  item_lock may be None.  result (5 elements, int64)
+    = set, expired, locked, the stored size, the stored encoding; status (1
+    element, int32) = STORE_OK, or STORE_FULL with nothing changed and result
+    zero; entry_status (uint8, one ENT_* per entry) is optional.  No host wait;
+    returns ``work`` (store_mset_work), which must outlive the stream's work."""
+    n, vlen = idx.numel(), value.numel()
+    if work is None:
+        work = store_mset_work(n, vlen, store.device)
+    rc = lib().lzf_gpu_store_mset(_ptr(idx), n, _ptr(value), vlen, int(compression), _ptr(store), int(store.numel()),
+                                  _ptr(store_used), _ptr(val_off), _ptr(val_size), _ptr(enc), _ptr(val_len),
+                                  int(enc.numel()), _ptr(item_time), _ptr(item_ttl), _opt_ptr(item_lock), int(now),
+                                  _opt_ptr(last_access), _opt_ptr(entry_status), _ptr(result), _ptr(status),
+                                  _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_mset")
+    return work
+
+
+def store_gc(last_access, now, gc_ratio, enc, val_size, result, gate=None, max_bytes=0, stream=None):
+    """The memory sweep over the whole store: a live item with now -
+    last_access != 0 and >= ``gc_ratio`` becomes ENC_NULL, whatever its lock
+    and TTL.  With ``gate`` (1 element, int64, normally store_used) the sweep
+    runs only when gate[0] > ``max_bytes``.  result (3 elements, int64) = items
+    freed, their stored bytes, 1 if the sweep ran.  No host wait."""
+    _check(lib().lzf_gpu_store_gc(_ptr(last_access), int(now), int(gc_ratio), _ptr(enc), _ptr(val_size),
+                                  int(enc.numel()), _opt_ptr(gate), int(max_bytes), _ptr(result),
+                                  _stream_handle(stream)), "lzf_gpu_store_gc")
+
+
+def meta_field(name):
+    """lzf_host_meta_field(): the META_* code gbGetItemMeta (src/query.c:
+    1255-1300) resolves a field name to, prefixes and over-long names as it
+    does, or None.  No GPU."""
+    name = bytes(name)
+    f = int(lib().lzf_host_meta_field(ctypes.c_char_p(name), len(name)))
+    return None if f < 0 else f
+
+
+def store_meta(idx, field, enc, val_size, item_time, item_ttl, item_lock, now, entry_value, result, last_access=None,
+               entry_status=None, stream=None):
+    """META over an index list: entry_value (int64, one per entry) receives the
+    field (a META_* code) of every valid entry, 0 otherwise; a valid entry then
+    gets last_access = now (META_ACCESS reports the value before), an expired
+    one becomes ENC_NULL.  item_lock may be None (0), last_access may be None
+    except for META_ACCESS.  result (2 elements, int64) = found, expired.  No
+    host wait."""
+    _check(lib().lzf_gpu_store_meta(_ptr(idx), int(idx.numel()), int(field), _ptr(enc), _ptr(val_size),
+                                    int(enc.numel()), _ptr(item_time), _ptr(item_ttl), _opt_ptr(item_lock), int(now),
+                                    _opt_ptr(last_access), _opt_ptr(entry_status), _ptr(entry_value), _ptr(result),
+                                    _stream_handle(stream)), "lzf_gpu_store_meta")
+
+
+def store_keys_work(n, device):
+    """A scratch tensor for one store_keys call over a list of ``n`` entries."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_keys_work_size(int(n))), dtype=torch.uint8, device=device)
+
+
+def store_keys(idx, keys, key_off, key_len, enc, frame, max_response, frame_len, result, work=None,
+               reply_header=True, stream=None):
+    """The KEYS reply over an index list: the j-th entry that is in range, not
+    ENC_NULL and has a key becomes the pair [decimal j -> the item's key, PLAIN]
+    of a KVAL frame as kv_frame writes it.  No validity test, nothing nulled.
+    result (2 elements, int64) = found, MGET_OK / MGET_NOT_FOUND /
+    MGET_TOO_BIG; frame_len (1 element, int64) is 0 unless MGET_OK.  No host
+    wait; returns ``work`` (store_keys_work), which must outlive the stream's
+    work."""
+    n = idx.numel()
+    if work is None:
+        work = store_keys_work(n, frame.device)
+    rc = lib().lzf_gpu_store_keys(_ptr(idx), n, _ptr(keys), _ptr(key_off), _ptr(key_len), _ptr(enc), int(enc.numel()),
+                                  1 if reply_header else 0, _ptr(frame), int(max_response), _ptr(frame_len),
+                                  _ptr(result), _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_keys")
+    return work
 
 
 def host_register(arr):

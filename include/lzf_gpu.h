@@ -691,6 +691,156 @@ int lzf_gpu_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, uin
                             uint8_t *refused /* may be NULL */, uint64_t *result /* 1 u64 */, void *stream);
 
 /*
+ * MSET by prefix: one new value for every entry of the list,
+ * gbQueryMultiSetHandler / gbMultiSetCallback (src/query.c:479-537).
+ *
+ * Per entry, in this order (:490-502): dead -> DEAD; locked -> LOCKED,
+ * untouched -- the lock is tested first, on an expired item too (:493 comes
+ * before :496); expired -> EXPIRED, nulled; otherwise the item is replaced by
+ * what gbSingleSet + gbCreateItem make (:375-425, :113-146) -> DONE: the new
+ * stored bytes, val_size[i] and enc[i], val_len[i] = vlen, item_time[i] =
+ * last_access[i] = now, item_ttl[i] = -1, and item_lock[i] = 0 when item_lock
+ * is given.  The item keeps its index and its key, so a key index over the
+ * store stays valid with no insert.
+ *
+ * The stored form is decided once, exactly as lzf_gpu_set_store decides it
+ * for that one value, bit for bit: the value is compressed iff vlen >
+ * compression, with out_len = vlen - 4 (for vlen < 4 the size wraps: no
+ * limit); with a stream the stored form is LZF_ENC_LZF and S is the stream's
+ * length, without one it is LZF_ENC_PLAIN, S = vlen and the input bytes.  The
+ * reference compresses the same bytes once per matched key; this call does it
+ * once.
+ *
+ * Placement: the k-th DONE entry in list order gets its own copy of the S
+ * bytes at val_off[i] = base + S * (DONE entries before k), base =
+ * *store_used, and *store_used = base + S * done.  The old bytes become dead
+ * space, which lzf_gpu_store_compact reclaims.  *status (one device u32):
+ * LZF_STORE_OK, or LZF_STORE_FULL when base + S * done > store_cap or the sum
+ * wraps.  Then nothing at all changes -- no array, not *store_used, not
+ * entry_status -- and result is all zero.
+ *
+ * result (5 device u64): [0] set (the reply of gbQueryMultiSetHandler; 0 ->
+ * REPL_ERR_NOT_FOUND), [1] expired, [2] locked, [3] S, [4] the stored
+ * encoding.  [3] and [4] are written on LZF_STORE_OK even when [0] is 0.  The
+ * STATS fold, which the reference applies once per key set (:400-405): when
+ * result[4] == LZF_ENC_LZF, lzf_host_store_stats over result[0] items that
+ * all have enc = LZF_ENC_LZF, val_size = result[3] and val_len = vlen.
+ *
+ * `value` (vlen device bytes) must not overlap the arena's free part
+ * [*store_used, store_cap): the copies are written there while the value is
+ * read.  That cannot be checked.  item_time and item_ttl are required (they
+ * are written); item_lock == NULL: nothing is locked.  LZF_GPU_EARG, before
+ * any HIP call: a NULL required pointer, n == 0, count == 0, store_cap == 0,
+ * vlen == 0 (the reference asserts vlen > 0), vlen > LZF_GPU_MAX_VALUE.
+ * work: lzf_gpu_store_mset_work_size(n, vlen) bytes of device scratch that
+ * must stay valid until the stream's work is done.  Asynchronous on `stream`,
+ * with no host wait; the list rules of the operators above apply.
+ */
+uint64_t lzf_gpu_store_mset_work_size(uint32_t n, uint32_t vlen);
+int lzf_gpu_store_mset(const uint32_t *idx, uint32_t n,
+                       const uint8_t *value, uint32_t vlen, uint32_t compression,
+                       uint8_t *store, uint64_t store_cap, uint64_t *store_used,
+                       uint64_t *val_off, uint32_t *val_size, uint8_t *enc, uint32_t *val_len, uint32_t count,
+                       int64_t *item_time, int32_t *item_ttl, int64_t *item_lock /* may be NULL */, int64_t now,
+                       int64_t *last_access /* may be NULL */, uint8_t *entry_status /* may be NULL */,
+                       uint64_t *result /* 5 u64 */, uint32_t *status, void *work, void *stream);
+
+/*
+ * The memory sweep, gbMemoryFreeHandler (src/server.c:311-327) over the whole
+ * store: for a live item, eta = now - last_access[i] in two's complement, and
+ * the item is freed (enc[i] = LZF_ENC_NULL) iff eta != 0 && eta >= gc_ratio,
+ * compared signed.  Locks and TTLs are not consulted; the reference does not
+ * consult them either.  result (3 device u64): [0] items freed, [1] the sum of
+ * their val_size -- what a lzf_gpu_store_compact will reclaim -- [2] 1 if the
+ * sweep ran.
+ *
+ * The gate is the cron's memused > maxmem (:401-411) without a host read:
+ * with gate != NULL (one device u64, normally store_used) the sweep runs only
+ * when *gate > max_bytes; otherwise nothing is written but result = {0, 0, 0}.
+ * gate == NULL: the sweep runs.  LZF_GPU_EARG: a NULL last_access, enc,
+ * val_size or result, count == 0.
+ */
+int lzf_gpu_store_gc(const int64_t *last_access, int64_t now, int64_t gc_ratio,
+                     uint8_t *enc, const uint32_t *val_size, uint32_t count,
+                     const uint64_t *gate /* may be NULL */, uint64_t max_bytes,
+                     uint64_t *result /* 3 u64 */, void *stream);
+
+/*
+ * META, gbQueryMetaHandler / gbGetItemMeta (src/query.c:1255-1339), over an
+ * index list.
+ *
+ * lzf_host_meta_field (host, no HIP call) resolves the field name exactly as
+ * gbGetItemMeta's chain does, quirks included: strncmp(m, name, min(mlen,
+ * strlen(name))) == 0, tried in the order size, encoding, access, created,
+ * ttl, left, lock.  So "s" and "sizeXYZ" are size, and "l" is left, not lock;
+ * a NUL inside m ends the comparison as strncmp does.  Returns the LZF_META_*
+ * code, or -1 (mlen == 0 and a NULL pointer included).  For an unknown field
+ * the reference still updates last_access on a valid item and replies
+ * REPL_ERR: that path is the host's reply plus lzf_gpu_store_count over the
+ * entry.
+ *
+ * lzf_gpu_store_meta, per entry: dead -> DEAD; expired -> EXPIRED and nulled
+ * (gbIsNodeStillValid, remove = 1); valid -> entry_value[k] is written, then
+ * last_access[i] = now -> DONE, so ACCESS reports the value before this call
+ * (:1322-1330).  Locks are not tested.  The values: SIZE val_size[i] (the
+ * stored size, as the reference), ENCODING enc[i], ACCESS last_access[i],
+ * CREATED item_time[i], TTL item_ttl[i], LEFT ttl <= 0 ? -1 : ttl - (now -
+ * item_time[i]), LOCK item_lock[i], or 0 when item_lock is NULL.
+ * entry_value[k] (n device i64, required) is 0 for entries that are not DONE.
+ * item_time and item_ttl are required; last_access may be NULL, but not for
+ * ACCESS.  result (2 device u64): [0] found, [1] expired.  LZF_GPU_EARG also
+ * for a field outside 0..6, n == 0, count == 0.
+ */
+#define LZF_META_SIZE      0
+#define LZF_META_ENCODING  1
+#define LZF_META_ACCESS    2
+#define LZF_META_CREATED   3
+#define LZF_META_TTL       4
+#define LZF_META_LEFT      5
+#define LZF_META_LOCK      6
+int lzf_host_meta_field(const uint8_t *m, uint32_t mlen);   /* code, or -1 */
+int lzf_gpu_store_meta(const uint32_t *idx, uint32_t n, int field, uint8_t *enc, const uint32_t *val_size,
+                       uint32_t count, const int64_t *item_time, const int32_t *item_ttl,
+                       const int64_t *item_lock /* may be NULL: 0 */, int64_t now,
+                       int64_t *last_access /* may be NULL, but not for ACCESS */,
+                       uint8_t *entry_status /* may be NULL */, int64_t *entry_value,
+                       uint64_t *result /* 2 u64: found, expired */, void *stream);
+
+/*
+ * The KEYS reply, gbQueryKeysHandler (src/query.c:1341-1391) after tr_search,
+ * over an index list (a lzf_gpu_store_select_prefix's output).
+ *
+ * An entry takes part iff it is in range, enc[i] != LZF_ENC_NULL and
+ * key_len[i] > 0.  The reference makes no validity test here: an expired item
+ * that has not been nulled takes part, nothing is nulled and last_access is
+ * not written.  The j-th participating entry in list order becomes the pair
+ *   [u32 ndigits][digits][u8 LZF_ENC_PLAIN][u32 key_len][key bytes]
+ * whose KVAL key is the decimal text of j ("%lu": "0", no leading zeros) and
+ * whose value is the item's key as a PLAIN item.  The pairs are preceded by
+ * [u32 found] and, with reply_header, by the 7-byte header -- byte for byte
+ * what lzf_gpu_kv_frame writes for the same pairs.
+ *
+ * result (2 device u64): [0] found, [1] LZF_MGET_OK, LZF_MGET_NOT_FOUND
+ * (found == 0) or LZF_MGET_TOO_BIG (the payload, header excluded, >
+ * max_response).  In the two last cases *frame_len = 0 and no frame byte is
+ * written; otherwise *frame_len is the frame's size, header included.  No byte
+ * at or past (reply_header ? 7 : 0) + max_response is ever written.
+ *
+ * Keys containing a NUL byte are outside the model: the reference truncates
+ * them through strlen (:1367), this call writes all key_len bytes.  Reply
+ * order is list order, not the reference's trie order.  work:
+ * lzf_gpu_store_keys_work_size(n) bytes of device scratch that must stay valid
+ * until the stream's work is done.  LZF_GPU_EARG: a NULL pointer, n == 0,
+ * count == 0.
+ */
+uint64_t lzf_gpu_store_keys_work_size(uint32_t n);
+int lzf_gpu_store_keys(const uint32_t *idx, uint32_t n,
+                       const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                       const uint8_t *enc, uint32_t count, int reply_header,
+                       uint8_t *frame, uint64_t max_response, uint64_t *frame_len,
+                       uint64_t *result /* 2 u64: found, LZF_MGET_* */, void *work, void *stream);
+
+/*
  * The device key index: exact-key lookup and upsert for the device store.
  *
  * The operators above address items by index.  The key index maps key bytes
