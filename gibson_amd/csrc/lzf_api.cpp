@@ -936,6 +936,52 @@ int lzf_gpu_store_mget(const uint32_t *idx, uint32_t n,
     return e == hipSuccess ? LZF_GPU_OK : code_of(e);
 }
 
+uint64_t lzf_gpu_store_replies_work_size(uint32_t n)
+{
+    return lzf_reply_work_bytes(n);
+}
+
+int lzf_gpu_store_replies(const uint32_t *idx, uint32_t n, int mode, const uint8_t *op_status,
+                          const uint8_t *store, const uint64_t *val_off, const uint32_t *val_size,
+                          uint8_t *enc, const uint32_t *val_len, uint32_t count,
+                          const int64_t *item_time, const int32_t *item_ttl, int64_t now,
+                          int64_t *last_access, uint32_t max_val_len,
+                          uint8_t *replies, uint64_t rep_cap, uint64_t *rep_used,
+                          uint64_t *rep_off, uint32_t *rep_len, uint8_t *entry_status,
+                          uint64_t *result, void *work, void *stream)
+{
+    if (!idx || !store || !val_off || !val_size || !enc || !val_len || !replies || !rep_used || !rep_off ||
+        !rep_len || !entry_status || !result || !work)
+        return LZF_GPU_EARG;
+    if (!n || !count || !item_time != !item_ttl) return LZF_GPU_EARG;
+    if (mode != LZF_REPLY_GET && mode != LZF_REPLY_VALUE) return LZF_GPU_EARG;
+    if ((mode == LZF_REPLY_VALUE) != (op_status != nullptr)) return LZF_GPU_EARG;
+    if (max_val_len > LZF_GPU_MAX_VALUE) return LZF_GPU_EARG;
+    int rc = current_device_ok();
+    if (rc) return rc;
+    /* one decode launch bounded by max_val_len, as MGET's, is the measured
+     * default; LZF_GPU_REPLY_ONE_ROUTE=0 runs one launch per
+     * decode size class.  Read per call, so one process can time both in turn */
+    const char *route = getenv("LZF_GPU_REPLY_ONE_ROUTE");
+    const bool one_route = !(route && !strcmp(route, "0"));
+    LzfReplyArgs a{};
+    a.idx = idx; a.n = n; a.mode = mode; a.op_status = op_status;
+    a.store = store; a.val_off = val_off; a.val_size = val_size;
+    a.enc = enc; a.val_len = val_len; a.count = count;
+    a.item_time = item_time; a.item_ttl = item_ttl; a.now = now; a.last_access = last_access;
+    a.max_val_len = max_val_len ? max_val_len : 1u;
+    a.replies = replies; a.rep_cap = rep_cap; a.rep_used = rep_used;
+    a.rep_off = rep_off; a.rep_len = rep_len; a.entry_status = entry_status; a.result = result;
+    lzf_reply_carve(a, work);
+    const hipError_t e = lzf_launch_store_replies(a, (hipStream_t)stream, launch_decompress, one_route);
+    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+}
+
+int lzf_host_reply_code(int ent_status)
+{
+    return lzf_reply_code(ent_status);
+}
+
 int lzf_gpu_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
                         const int64_t *item_time, const int32_t *item_ttl, int64_t now,
                         int64_t *last_access, uint64_t *result, void *stream)

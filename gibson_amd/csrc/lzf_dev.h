@@ -5,7 +5,8 @@
  * kernels (lzf_store.hip, lzf_mget.hip) with the carry scan over tile sums
  * (lzf_mset.hip, lzf_meta.hip); and the per-item rules the index-list
  * operators share (lzf_mget.hip, lzf_ops.hip, lzf_mset.hip, lzf_meta.hip):
- * validity, lock, number parse.
+ * validity, lock, number parse; and the size-class rule (lzf_mixed.hip,
+ * lzf_reply.hip) and the reply code of an entry status (lzf_reply.hip).
  */
 #ifndef GIBSON_AMD_LZF_DEV_H
 #define GIBSON_AMD_LZF_DEV_H
@@ -253,6 +254,47 @@ __host__ __device__ inline int lzf_parse_long(const uint8_t *v, uint32_t len, in
     }
     *out = (int64_t)(neg ? 0ull - n : n);
     return 1;
+}
+
+/* The size classes.  Compress, by in_len: the edges of the routing's value
+ * sizes (lane_min_count and LANE_DEFAULT_MAX of lzf_api.cpp; window64 past
+ * 64 KiB).  Decompress, by out_cap: tokpar64 up to 4 KiB, tokpar64-far up to
+ * CD_FAR_MAX (16 KiB), the pipe past it (lzf_launch_decompress).  A length
+ * past the caller's bound is refused: class LZF_GPU_NCLASS.  The only place
+ * the edges are written: lzf_decode_class_edge names the decode ones. */
+#define LZF_DECODE_NCLASS 3u
+#define LZF_DECODE_EDGE0  4096u
+#define LZF_DECODE_EDGE1  16384u
+static __host__ __device__ inline uint32_t lzf_size_class_of(uint32_t len, uint32_t bound, int kind)
+{
+    if (len > bound) return (uint32_t)LZF_GPU_NCLASS;
+    if (kind == LZF_GPU_KIND_COMPRESS)
+        return len <= 4096u ? 0u : len <= 8192u ? 1u : len <= 16384u ? 2u : len <= 65536u ? 3u : 4u;
+    return len <= LZF_DECODE_EDGE0 ? 0u : len <= LZF_DECODE_EDGE1 ? 1u : 2u;
+}
+
+/* the largest out_cap of decode class c; the last class has none */
+static inline uint32_t lzf_decode_class_edge(uint32_t c)
+{
+    return c == 0u ? LZF_DECODE_EDGE0 : c == 1u ? LZF_DECODE_EDGE1 : 0xFFFFFFFFu;
+}
+
+/* The reply code of an operator's entry status, the single-key replies of
+ * gbQueryIncDecHandler and its kin (src/query.c:853-886): REPL_VAL for an
+ * entry the operator applied to, the error code of the others.  One rule for
+ * the reply kernels and lzf_host_reply_code */
+__host__ __device__ inline int lzf_reply_code_of(int ent_status)
+{
+    switch (ent_status) {
+    case LZF_ENT_DONE:
+    case LZF_ENT_CONVERTED: return LZF_REPL_VAL;
+    case LZF_ENT_DEAD:
+    case LZF_ENT_EXPIRED: return LZF_REPL_ERR_NOT_FOUND;
+    case LZF_ENT_LOCKED: return LZF_REPL_ERR_LOCKED;
+    case LZF_ENT_NAN:
+    case LZF_ENT_UNCHANGED: return LZF_REPL_ERR_NAN;
+    default: return LZF_REPL_ERR;
+    }
 }
 
 #endif

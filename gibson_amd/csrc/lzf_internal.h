@@ -142,6 +142,44 @@ struct LzfMgetArgs {
     uint8_t *g_enc, *w_skip;
 };
 
+/* the per-request replies over an index list (lzf_reply.hip); device pointers.
+ * op_status: VALUE mode only */
+struct LzfReplyArgs {
+    const uint32_t *idx;
+    uint32_t n;
+    int mode;
+    const uint8_t *op_status;
+    const uint8_t *store;
+    const uint64_t *val_off;
+    const uint32_t *val_size;
+    uint8_t *enc;
+    const uint32_t *val_len;
+    uint32_t count;
+    const int64_t *item_time;
+    const int32_t *item_ttl;
+    int64_t now;
+    int64_t *last_access;
+    uint32_t max_val_len;
+    uint8_t *replies;
+    uint64_t rep_cap;
+    uint64_t *rep_used;
+    uint64_t *rep_off;
+    uint32_t *rep_len;
+    uint8_t *entry_status;
+    uint64_t *result;
+    /* work area (lzf_reply_carve).  g_*: the entries' descriptors in list order
+     * (g_code: the entry's LZF_REPL_* code; g_cls: its decode class, RP_NO_CLASS
+     * when the decoder has nothing to do for it; g_null: the item an expired
+     * entry nulls); w_off: the slot's offset inside its tile; per tile the slot
+     * bytes, then the bytes before it, and the packed counts; w_voff, w_len,
+     * w_err: the decoder's out_off, out_len, err; w_skip: one skip list per
+     * decode class */
+    uint64_t *w_state, *g_val_off, *w_off, *w_voff, *w_tile, *w_tcnt;
+    uint32_t *g_val_size, *g_val_len, *g_null, *w_len;
+    int32_t *w_err;
+    uint8_t *g_enc, *g_code, *g_cls, *w_skip;
+};
+
 /* the key index over the store's keys (lzf_kidx.hip); device pointers.  The
  * lookup reads table, slots, the key arrays, enc, count and result only */
 struct LzfKidxArgs {
@@ -362,6 +400,15 @@ hipError_t lzf_launch_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc,
 hipError_t lzf_launch_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *enc, uint32_t count,
                                  int64_t *item_time, int32_t *item_ttl, int64_t now, int64_t *last_access,
                                  uint64_t *result, hipStream_t s);
+/* one reply frame per entry of an index list (lzf_reply.hip): classify, scan,
+ * write, `decode` once per decode size class (one_route: once, with
+ * max_val_len) over the gathered entries, in place in the arena, check; and
+ * the reply code of an entry status on the host */
+hipError_t lzf_launch_store_replies(LzfReplyArgs &a, hipStream_t s,
+                                    hipError_t (*decode)(const LzfBatch &, hipStream_t), bool one_route);
+uint64_t lzf_reply_work_bytes(uint32_t n);
+void lzf_reply_carve(LzfReplyArgs &a, void *work);
+int lzf_reply_code(int ent_status);
 /* the lock-aware operators over an index list (lzf_ops.hip): MLOCK, MUNLOCK
  * and MDEL in one pass each, INC / DEC in three launches, the SET guard over
  * a lookup's output, and the number parse on the host */

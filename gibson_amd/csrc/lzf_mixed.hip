@@ -8,9 +8,9 @@
  * large value moves a whole batch to the plan its size needs (DESIGN.md
  * §4.0).  The mixed calls (lzf_gpu_compress_mixed / lzf_gpu_decompress_mixed,
  * lzf_api.cpp) partition the batch by the size edges that routing already
- * uses and run every class as a batch of its own.  This file holds the rule
- * (lzf_size_class_of, the only place the edges are written) and the kernels
- * that apply it; the codec kernels are untouched.
+ * uses and run every class as a batch of its own.  The rule is
+ * lzf_size_class_of (lzf_dev.h, the only place the edges are written); this
+ * file holds the kernels that apply it; the codec kernels are untouched.
  *
  * Partition, three launches on one stream (no workgroup waits for another):
  *   1. lzf_mixed_hist_kernel: a workgroup of 4 waves takes a tile of 2048
@@ -30,7 +30,7 @@
  */
 #include <errno.h>
 
-#include "lzf_internal.h"
+#include "lzf_dev.h"
 #include "../../include/lzf_gpu.h"
 
 #define MX_NC      (LZF_GPU_NCLASS + 1)   /* the classes and "refused" */
@@ -40,18 +40,8 @@
 #define MX_WAVES   (MX_THREADS / 64u)
 #define MX_SEGS    (MX_ROUNDS * MX_WAVES)
 
-/* The size classes.  Compress, by in_len: the edges of the routing's value
- * sizes (lane_min_count and LANE_DEFAULT_MAX of lzf_api.cpp; window64 past
- * 64 KiB).  Decompress, by out_cap: tokpar64 up to 4 KiB, tokpar64-far up to
- * CD_FAR_MAX (16 KiB), the pipe past it (lzf_launch_decompress).  A length
- * past the caller's bound is refused: class LZF_GPU_NCLASS. */
-static __host__ __device__ inline uint32_t lzf_size_class_of(uint32_t len, uint32_t bound, int kind)
-{
-    if (len > bound) return (uint32_t)LZF_GPU_NCLASS;
-    if (kind == LZF_GPU_KIND_COMPRESS)
-        return len <= 4096u ? 0u : len <= 8192u ? 1u : len <= 16384u ? 2u : len <= 65536u ? 3u : 4u;
-    return len <= 4096u ? 0u : len <= 16384u ? 1u : 2u;
-}
+/* lzf_size_class_of, the class rule and the only place the edges are written:
+ * lzf_dev.h */
 
 static inline uint32_t mx_tiles(uint32_t count)
 {

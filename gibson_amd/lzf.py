@@ -81,6 +81,9 @@ EXPORTS = (
     "lzf_gpu_store_meta",
     "lzf_gpu_store_keys_work_size",
     "lzf_gpu_store_keys",
+    "lzf_gpu_store_replies_work_size",
+    "lzf_gpu_store_replies",
+    "lzf_host_reply_code",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -97,12 +100,19 @@ MGET_OK, MGET_NOT_FOUND, MGET_TOO_BIG, MGET_EDECODE = 0, 1, 2, 3
 KIDX_OK, KIDX_FULL = 0, 1
 # entry_status of store_mlock / _munlock / _mdel / _minc (include/lzf_gpu.h)
 ENT_DONE, ENT_DEAD, ENT_EXPIRED, ENT_LOCKED, ENT_NAN, ENT_CONVERTED, ENT_UNCHANGED = 0, 1, 2, 3, 4, 5, 6
+# entry_status of store_replies: an LZF item did not decode to val_len
+ENT_EDECODE = 7
+# mode and result[3] of store_replies (include/lzf_gpu.h)
+REPLY_GET, REPLY_VALUE = 0, 1
+REPLY_OK, REPLY_TOO_BIG = 0, 1
 # field of store_meta, as meta_field resolves a name (include/lzf_gpu.h)
 META_SIZE, META_ENCODING, META_ACCESS, META_CREATED, META_TTL, META_LEFT, META_LOCK = 0, 1, 2, 3, 4, 5, 6
 
 # item encodings (src/net.h:274-278) and the MGET reply code (src/query.h:71)
 ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
 REPL_KVAL = 7
+# the reply codes of store_replies (src/query.h:64-70)
+REPL_ERR, REPL_ERR_NOT_FOUND, REPL_ERR_NAN, REPL_ERR_LOCKED, REPL_OK, REPL_VAL = 0, 1, 2, 4, 5, 6
 
 
 class LzfLibraryMissing(ImportError):
@@ -216,6 +226,8 @@ def _load(path):
         _bind_store_ops(L)
     if hasattr(L, "lzf_gpu_store_mset"):
         _bind_store_mset(L)
+    if hasattr(L, "lzf_gpu_store_replies"):
+        _bind_store_replies(L)
     del i32
     _LOADED[path] = L
     return L
@@ -353,6 +365,19 @@ def _bind_store_mset(L):
     L.lzf_gpu_store_keys_work_size.argtypes = [u32]
     L.lzf_gpu_store_keys.restype = ctypes.c_int
     L.lzf_gpu_store_keys.argtypes = [vp, u32, vp, vp, vp, vp, u32, ctypes.c_int, vp, u64, vp, vp, vp, vp]
+
+
+def _bind_store_replies(L):
+    """The per-request replies of the device store; absent from an older build
+    given by LZF_HIP_LIB (the helpers below then raise AttributeError)."""
+    u32, u64, vp, i64 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64
+    L.lzf_gpu_store_replies_work_size.restype = u64
+    L.lzf_gpu_store_replies_work_size.argtypes = [u32]
+    L.lzf_gpu_store_replies.restype = ctypes.c_int
+    L.lzf_gpu_store_replies.argtypes = [vp, u32, ctypes.c_int, vp, vp, vp, vp, vp, vp, u32, vp, vp, i64, vp, u32,
+                                        vp, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.lzf_host_reply_code.restype = ctypes.c_int
+    L.lzf_host_reply_code.argtypes = [ctypes.c_int]
 
 
 def selfcheck():
@@ -734,6 +759,47 @@ def store_mget(idx, keys, key_off, key_len, store, val_off, val_size, enc, val_l
                                   _ptr(result), _ptr(work), _stream_handle(stream))
     _check(rc, "lzf_gpu_store_mget")
     return work
+
+
+def store_replies_work(n, device):
+    """A scratch tensor for one store_replies call over a list of ``n`` entries."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_replies_work_size(int(n))), dtype=torch.uint8, device=device)
+
+
+def store_replies(idx, mode, store, val_off, val_size, enc, val_len, item_time, item_ttl, now, max_val_len, replies,
+                  rep_used, rep_off, rep_len, entry_status, result, op_status=None, last_access=None, work=None,
+                  stream=None):
+    """One reply frame per entry of the index list ``idx`` (int32, read as
+    u32), packed into the arena ``replies`` (uint8; its length is the cap) in
+    list order: reply k is replies[rep_off[k] : rep_off[k] + rep_len[k]],
+    ``[i16 code][u8 encoding][u32 size][bytes]``, LZF items decoded in place.
+    REPLY_GET applies the validity rule as store_mget does (op_status None);
+    REPLY_VALUE maps op_status (uint8, one ENT_* per entry, as store_minc
+    leaves it) to the reply codes and writes neither enc nor last_access.
+    rep_used (1 element, int64), rep_off (n, int64), rep_len (n, int32),
+    entry_status (n, uint8, ENT_EDECODE for an item that did not decode);
+    result (6 elements, int64) = item replies, expired, dead or code replies,
+    REPLY_*, bytes needed, decode failures.  On REPLY_TOO_BIG no arena byte is
+    written and rep_used is 0.  No host wait; returns ``work``
+    (store_replies_work), which must outlive the stream's work."""
+    n = idx.numel()
+    if work is None:
+        work = store_replies_work(n, replies.device)
+    rc = lib().lzf_gpu_store_replies(_ptr(idx), n, int(mode), _opt_ptr(op_status), _ptr(store), _ptr(val_off),
+                                     _ptr(val_size), _ptr(enc), _ptr(val_len), int(enc.numel()), _opt_ptr(item_time),
+                                     _opt_ptr(item_ttl), int(now), _opt_ptr(last_access), int(max_val_len),
+                                     _ptr(replies), int(replies.numel()), _ptr(rep_used), _ptr(rep_off),
+                                     _ptr(rep_len), _ptr(entry_status), _ptr(result), _ptr(work),
+                                     _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_replies")
+    return work
+
+
+def reply_code(ent_status):
+    """lzf_host_reply_code: the REPL_* code of an ENT_* entry status, the rule
+    store_replies applies in REPLY_VALUE mode.  No device call."""
+    return int(lib().lzf_host_reply_code(int(ent_status)))
 
 
 def store_count(idx, enc, item_time, item_ttl, now, result, last_access=None, stream=None):

@@ -873,10 +873,9 @@ int lzf_gpu_store_keys(const uint32_t *idx, uint32_t n,
  *
  * Locks: SET on a locked item replies REPL_ERR_LOCKED (src/query.c:446-451);
  * lzf_gpu_store_set_guard, run between the lookup of a batch's own keys and
- * its insert, decides that on the device.  Not modelled: the single-item GET
- * reply (gbClientEnqueueItem) -- the lookup yields the index, and the KVAL
- * frame of lzf_gpu_store_mget is what the device writes; the ordered prefix
- * walk, which stays with the host's trie.
+ * its insert, decides that on the device.  Not modelled: the ordered prefix
+ * walk, which stays with the host's trie, and the SET reply, which the host
+ * builds from the request's bytes it holds.
  */
 #define LZF_KIDX_OK    0
 #define LZF_KIDX_FULL  1   /* *used + n > slots - slots / 4: the batch was refused as a whole */
@@ -946,6 +945,108 @@ int lzf_gpu_key_index_lookup(const void *table, uint32_t slots,
                              const uint8_t *enc, uint32_t count,
                              const uint8_t *qkeys, const uint64_t *q_off, const uint32_t *q_len, uint32_t nq,
                              uint32_t *idx, uint64_t *result /* 3 u64 */, void *stream);
+
+/*
+ * Per-request replies over an index list: the reply of GET, and of the
+ * single-key INC / DEC, for the requests of many clients batched into one
+ * list (lzf_gpu_key_index_lookup yields it).  For n entries the call writes n
+ * self-contained reply frames into one reply arena in device memory, LZF
+ * items decoded in place, asynchronously on `stream` with no host wait:
+ * lookup -> replies -> one copy of replies[0 .. *rep_used), rep_off, rep_len.
+ *
+ * A reply is the buffer of gbClientEnqueueData (src/net.c:1170-1202):
+ *   [i16 code LE][u8 encoding][u32 size LE][size bytes]
+ * A code reply is gbClientEnqueueCode's form of it: encoding PLAIN, size 1,
+ * one 0x00 byte -- 8 bytes.  An item reply is gbClientEnqueueItem's
+ * (src/net.c:1216-1254), code REPL_VAL, by the item's encoding:
+ *   PLAIN   the val_size stored bytes;
+ *   NUMBER  the stored bytes, encoding NUMBER;
+ *   LZF     encoding PLAIN, size val_len, the value decoded straight into the
+ *           reply.
+ * The framing is a restatement of src/net.c, not compared with a build of it.
+ *
+ * mode LZF_REPLY_GET, gbQueryGetHandler (src/query.c:634-663): the validity
+ * rule as MGET applies it.  A dead, out-of-range or padding entry is
+ * LZF_ENT_DEAD and gets a REPL_ERR_NOT_FOUND code reply; an expired entry is
+ * LZF_ENT_EXPIRED, is nulled in enc and gets the same reply; a valid entry is
+ * LZF_ENT_DONE, gets last_access[i] = now and its item reply.  Every copy of a
+ * duplicated entry is judged on what enc held before the call and gets a
+ * reply of its own: two clients asking for one key are the normal case.
+ * op_status must be NULL.
+ *
+ * mode LZF_REPLY_VALUE, the reply after an operator that left entry_status
+ * (lzf_gpu_store_minc(single = 1)): no validity rule is applied and neither
+ * enc nor last_access is written.  op_status[k] (n device bytes, required) is
+ * mapped by the rule of lzf_host_reply_code: DONE and CONVERTED -> REPL_VAL,
+ * an item reply of item idx[k] as it now stands; DEAD and EXPIRED ->
+ * REPL_ERR_NOT_FOUND; LOCKED -> REPL_ERR_LOCKED; NAN and UNCHANGED ->
+ * REPL_ERR_NAN; anything else -> REPL_ERR.  An entry mapped to REPL_VAL whose
+ * idx[k] >= count or whose enc[idx[k]] is LZF_ENC_NULL gets REPL_ERR.
+ * entry_status[k] = op_status[k] (but for decode failures, below); the two
+ * may be the same array.
+ *
+ * The arena.  Replies are packed densely in list order from byte 0.  The slot
+ * of a reply is max(8, 7 + size) bytes -- a size-0 PLAIN item writes 7 bytes
+ * into an 8-byte slot -- rep_off[k] is the exclusive sum of the slots,
+ * rep_len[k] the reply's byte count and *rep_used the sum of the slots.  No
+ * byte at or past rep_cap is ever written.  If the slots do not fit in
+ * rep_cap the call is LZF_REPLY_TOO_BIG: no arena byte is written and
+ * *rep_used = 0, while rep_off, rep_len and entry_status are written as they
+ * would have been and result[4] holds the bytes needed, so the host retries
+ * with a larger arena.  GET's nulling and last_access happen whatever the
+ * status, as in MGET.
+ *
+ * Decode failures are per entry.  An LZF item fails when it does not decode
+ * to exactly val_len bytes: a decoder error, a wrong length, or val_len >
+ * max_val_len (above LZF_GPU_MAX_VALUE: LZF_GPU_EARG).  The entry is
+ * LZF_ENT_EDECODE, a REPL_ERR code reply stands at the start of its slot,
+ * rep_len[k] = 8, the rest of its slot is unspecified and nothing outside it
+ * is touched; the other replies are unaffected.  An item refused for val_len >
+ * max_val_len is known before the layout is made and takes an 8-byte slot.
+ * The decoder runs once over the list, bounded by max_val_len, as MGET's does.
+ * LZF_GPU_REPLY_ONE_ROUTE=0 (diagnostics) runs it once per decode size class
+ * (lzf_gpu_size_class) instead, each launch over its own entries with its
+ * class's bound and still with no host wait; that form measured slower on a
+ * list of mixed sizes, so it is not the default.
+ *
+ * result (6 device u64): [0] item replies, [1] entries this call expired,
+ * [2] dead or skipped entries -- in VALUE mode: the code replies -- [3] one of
+ * LZF_REPLY_*, [4] the bytes needed, [5] decode failures.  [0] + [1] + [2] +
+ * [5] == n.  On LZF_REPLY_TOO_BIG nothing is decoded: [5] counts the refused
+ * items only.
+ *
+ * LZF_GPU_EARG, before any HIP call: a NULL pointer but the optional ones,
+ * n == 0, count == 0, a bad mode, op_status not matching the mode, exactly
+ * one of item_time / item_ttl NULL, max_val_len > LZF_GPU_MAX_VALUE.  work:
+ * lzf_gpu_store_replies_work_size(n) bytes of device scratch that must stay
+ * valid until the stream's work is done.  The SET reply stays with the host.
+ */
+#define LZF_REPL_ERR            0   /* src/query.h:64-70 */
+#define LZF_REPL_ERR_NOT_FOUND  1
+#define LZF_REPL_ERR_NAN        2
+#define LZF_REPL_ERR_LOCKED     4
+#define LZF_REPL_OK             5
+#define LZF_REPL_VAL            6
+#define LZF_ENT_EDECODE         7   /* replies: an LZF item did not decode to val_len */
+
+#define LZF_REPLY_GET    0   /* gbQueryGetHandler, src/query.c:634-663 */
+#define LZF_REPLY_VALUE  1   /* after an operator that left entry_status (single-key INC / DEC) */
+
+#define LZF_REPLY_OK       0
+#define LZF_REPLY_TOO_BIG  1   /* the slots do not fit in rep_cap */
+
+uint64_t lzf_gpu_store_replies_work_size(uint32_t n);
+int lzf_gpu_store_replies(const uint32_t *idx, uint32_t n, int mode,
+                          const uint8_t *op_status /* VALUE: n LZF_ENT_* bytes, required; GET: must be NULL */,
+                          const uint8_t *store, const uint64_t *val_off, const uint32_t *val_size,
+                          uint8_t *enc, const uint32_t *val_len, uint32_t count,
+                          const int64_t *item_time, const int32_t *item_ttl, int64_t now,
+                          int64_t *last_access /* may be NULL */, uint32_t max_val_len,
+                          uint8_t *replies, uint64_t rep_cap, uint64_t *rep_used,
+                          uint64_t *rep_off /* n */, uint32_t *rep_len /* n */, uint8_t *entry_status /* n */,
+                          uint64_t *result /* 6 u64 */, void *work, void *stream);
+/* host, no HIP call: the LZF_REPL_* code of an LZF_ENT_* entry status */
+int lzf_host_reply_code(int ent_status);
 
 /* Free the library's device scratch (all devices), the calling thread's and
  * the device workers' staging buffers; later calls allocate them again.
