@@ -427,6 +427,18 @@ int code_of(hipError_t e)
     return LZF_GPU_ELAUNCH;
 }
 
+/* what an entry point returns for its launcher's result */
+int rc_of(hipError_t e) { return e == hipSuccess ? LZF_GPU_OK : code_of(e); }
+
+/* the store's item arrays as the one view the launchers take (LzfItems).  Its
+ * members are not const; a call site whose operator only reads an array casts
+ * there and says so */
+LzfItems items_of(uint8_t *enc, uint32_t count, int64_t *item_time, int32_t *item_ttl, int64_t *item_lock,
+                  int64_t *last_access, int64_t now)
+{
+    return LzfItems{enc, count, item_time, item_ttl, item_lock, last_access, now};
+}
+
 /* ---- mixed-size batches: one class batch per size class -------------------- */
 
 constexpr uint32_t MIXED_NC = LZF_GPU_NCLASS + 1;
@@ -802,8 +814,7 @@ int lzf_gpu_set_store(const uint8_t *in, const uint64_t *in_off, const uint32_t 
         !status || !work)
         return LZF_GPU_EARG;
     if (max_in_len > LZF_GPU_MAX_VALUE || !store_cap) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfStoreArgs a{};
     a.in = in; a.in_off = in_off; a.in_len = in_len;
     a.count = count; a.max_in_len = max_in_len; a.compression = compression;
@@ -811,28 +822,26 @@ int lzf_gpu_set_store(const uint8_t *in, const uint64_t *in_off, const uint32_t 
     a.store = store; a.store_cap = store_cap; a.store_used = store_used;
     a.val_off = val_off; a.val_size = val_size; a.enc = enc; a.status = status;
     lzf_store_carve(a, work);
-    const hipError_t e = lzf_launch_store(a, (hipStream_t)stream, store_compress);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store(a, (hipStream_t)stream, store_compress));
 }
 
 int lzf_gpu_store_delete(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count, void *stream)
 {
     if (!idx || !enc || !count) return LZF_GPU_EARG;
     if (!n) return LZF_GPU_OK;
-    int rc = current_device_ok();
-    if (rc) return rc;
-    const hipError_t e = lzf_launch_store_delete(idx, n, enc, count, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    if (const int rc = current_device_ok()) return rc;
+    return rc_of(lzf_launch_store_delete(idx, n, enc, count, (hipStream_t)stream));
 }
 
 int lzf_gpu_store_expire(const int64_t *item_time, const int32_t *ttl, int64_t now,
                          uint8_t *enc, uint32_t count, uint32_t *expired, void *stream)
 {
     if (!item_time || !ttl || !enc || !expired || !count) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
-    const hipError_t e = lzf_launch_store_expire(item_time, ttl, now, enc, count, expired, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    if (const int rc = current_device_ok()) return rc;
+    /* the sweep reads the time arrays only */
+    const LzfItems it = items_of(enc, count, const_cast<int64_t *>(item_time), const_cast<int32_t *>(ttl), nullptr,
+                                 nullptr, now);
+    return rc_of(lzf_launch_store_expire(it, expired, (hipStream_t)stream));
 }
 
 uint64_t lzf_gpu_store_compact_work_size(uint32_t count)
@@ -844,14 +853,12 @@ int lzf_gpu_store_usage(const uint32_t *val_size, const uint8_t *enc, uint32_t c
                         uint64_t *report, void *work, void *stream)
 {
     if (!val_size || !enc || !count || !report || !work) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfCompactArgs a{};
     a.val_size = const_cast<uint32_t *>(val_size);         /* usage only reads */
     a.enc = enc; a.count = count; a.report = report;
     lzf_compact_carve(a, work);
-    const hipError_t e = lzf_launch_store_usage(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_usage(a, (hipStream_t)stream));
 }
 
 int lzf_gpu_store_compact(const uint8_t *src, uint64_t src_cap,
@@ -866,16 +873,14 @@ int lzf_gpu_store_compact(const uint8_t *src, uint64_t src_cap,
     const uint64_t s0 = (uint64_t)(uintptr_t)src, d0 = (uint64_t)(uintptr_t)dst;
     const uint64_t s1 = s0 + src_cap < s0 ? ~0ull : s0 + src_cap, d1 = d0 + dst_cap < d0 ? ~0ull : d0 + dst_cap;
     if (d0 < s1 && s0 < d1) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfCompactArgs a{};
     a.src = src; a.src_cap = src_cap;
     a.val_off = val_off; a.val_size = val_size; a.enc = enc; a.count = count;
     a.dst = dst; a.dst_cap = dst_cap; a.dst_used = dst_used;
     a.report = report; a.status = status;
     lzf_compact_carve(a, work);
-    const hipError_t e = lzf_launch_store_compact(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_compact(a, (hipStream_t)stream));
 }
 
 uint64_t lzf_gpu_store_select_work_size(uint32_t count)
@@ -890,15 +895,13 @@ int lzf_gpu_store_select_prefix(const uint8_t *keys, const uint64_t *key_off, co
 {
     if (!keys || !key_off || !key_len || !enc || !prefix || !sel || !result || !work) return LZF_GPU_EARG;
     if (!count || !prefix_len || !cap) return LZF_GPU_EARG;   /* the reference asserts len > 0 */
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfSelectArgs a{};
     a.keys = keys; a.key_off = key_off; a.key_len = key_len; a.enc = enc; a.count = count;
     a.prefix = prefix; a.prefix_len = prefix_len;
     a.sel = sel; a.cap = cap; a.result = result;
     lzf_select_carve(a, work);
-    const hipError_t e = lzf_launch_store_select(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_select(a, (hipStream_t)stream));
 }
 
 uint64_t lzf_gpu_store_mget_work_size(uint32_t n)
@@ -920,20 +923,19 @@ int lzf_gpu_store_mget(const uint32_t *idx, uint32_t n,
         return LZF_GPU_EARG;
     if (!n || !count || !item_time != !item_ttl) return LZF_GPU_EARG;
     if (max_val_len > LZF_GPU_MAX_VALUE) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfMgetArgs a{};
     a.idx = idx; a.n = n;
     a.keys = keys; a.key_off = key_off; a.key_len = key_len;
-    a.store = store; a.val_off = val_off; a.val_size = val_size;
-    a.enc = enc; a.val_len = val_len; a.count = count;
-    a.item_time = item_time; a.item_ttl = item_ttl; a.now = now; a.last_access = last_access;
+    a.store = store; a.val_off = val_off; a.val_size = val_size; a.val_len = val_len;
+    /* MGET reads the time arrays only */
+    a.it = items_of(enc, count, const_cast<int64_t *>(item_time), const_cast<int32_t *>(item_ttl), nullptr, last_access,
+                    now);
     a.max_val_len = max_val_len ? max_val_len : 1u;
     a.reply_header = reply_header;
     a.frame = frame; a.max_response = max_response; a.frame_len = frame_len; a.result = result;
     lzf_mget_carve(a, work);
-    const hipError_t e = lzf_launch_store_mget(a, (hipStream_t)stream, launch_decompress);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_mget(a, (hipStream_t)stream, launch_decompress));
 }
 
 uint64_t lzf_gpu_store_replies_work_size(uint32_t n)
@@ -957,8 +959,7 @@ int lzf_gpu_store_replies(const uint32_t *idx, uint32_t n, int mode, const uint8
     if (mode != LZF_REPLY_GET && mode != LZF_REPLY_VALUE) return LZF_GPU_EARG;
     if ((mode == LZF_REPLY_VALUE) != (op_status != nullptr)) return LZF_GPU_EARG;
     if (max_val_len > LZF_GPU_MAX_VALUE) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     /* one decode launch bounded by max_val_len, as MGET's, is the measured
      * default; LZF_GPU_REPLY_ONE_ROUTE=0 runs one launch per
      * decode size class.  Read per call, so one process can time both in turn */
@@ -966,15 +967,15 @@ int lzf_gpu_store_replies(const uint32_t *idx, uint32_t n, int mode, const uint8
     const bool one_route = !(route && !strcmp(route, "0"));
     LzfReplyArgs a{};
     a.idx = idx; a.n = n; a.mode = mode; a.op_status = op_status;
-    a.store = store; a.val_off = val_off; a.val_size = val_size;
-    a.enc = enc; a.val_len = val_len; a.count = count;
-    a.item_time = item_time; a.item_ttl = item_ttl; a.now = now; a.last_access = last_access;
+    a.store = store; a.val_off = val_off; a.val_size = val_size; a.val_len = val_len;
+    /* the replies read the time arrays only */
+    a.it = items_of(enc, count, const_cast<int64_t *>(item_time), const_cast<int32_t *>(item_ttl), nullptr, last_access,
+                    now);
     a.max_val_len = max_val_len ? max_val_len : 1u;
     a.replies = replies; a.rep_cap = rep_cap; a.rep_used = rep_used;
     a.rep_off = rep_off; a.rep_len = rep_len; a.entry_status = entry_status; a.result = result;
     lzf_reply_carve(a, work);
-    const hipError_t e = lzf_launch_store_replies(a, (hipStream_t)stream, launch_decompress, one_route);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_replies(a, (hipStream_t)stream, launch_decompress, one_route));
 }
 
 int lzf_host_reply_code(int ent_status)
@@ -987,11 +988,11 @@ int lzf_gpu_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t 
                         int64_t *last_access, uint64_t *result, void *stream)
 {
     if (!idx || !enc || !result || !n || !count || !item_time != !item_ttl) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
-    const hipError_t e = lzf_launch_store_count(idx, n, enc, count, item_time, item_ttl, now, last_access, result,
-                                                (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    if (const int rc = current_device_ok()) return rc;
+    /* COUNT reads the time arrays only */
+    const LzfItems it = items_of(enc, count, const_cast<int64_t *>(item_time), const_cast<int32_t *>(item_ttl), nullptr,
+                                 last_access, now);
+    return rc_of(lzf_launch_store_count(idx, n, it, result, (hipStream_t)stream));
 }
 
 int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *enc, uint32_t count,
@@ -999,11 +1000,9 @@ int lzf_gpu_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *en
                        int64_t *last_access, uint64_t *result, void *stream)
 {
     if (!idx || !enc || !item_time || !item_ttl || !result || !n || !count) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
-    const hipError_t e = lzf_launch_store_mttl(idx, n, ttl, enc, count, item_time, item_ttl, now, last_access, result,
-                                               (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    if (const int rc = current_device_ok()) return rc;
+    const LzfItems it = items_of(enc, count, item_time, item_ttl, nullptr, last_access, now);
+    return rc_of(lzf_launch_store_mttl(idx, n, ttl, it, result, (hipStream_t)stream));
 }
 
 int lzf_gpu_store_mlock(const uint32_t *idx, uint32_t n, int64_t lock_time, uint8_t *enc, uint32_t count,
@@ -1011,14 +1010,13 @@ int lzf_gpu_store_mlock(const uint32_t *idx, uint32_t n, int64_t lock_time, uint
                         int64_t *last_access, uint8_t *entry_status, uint64_t *result, void *stream)
 {
     if (!idx || !enc || !item_time || !item_ttl || !item_lock || !result || !n || !count) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfLockArgs a{};
-    a.idx = idx; a.n = n; a.lock_time = lock_time; a.enc = enc; a.count = count;
-    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
-    a.last_access = last_access; a.entry_status = entry_status; a.result = result;
-    const hipError_t e = lzf_launch_store_mlock(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    a.idx = idx; a.n = n; a.lock_time = lock_time;
+    /* MLOCK only reads the ttl */
+    a.it = items_of(enc, count, item_time, const_cast<int32_t *>(item_ttl), item_lock, last_access, now);
+    a.entry_status = entry_status; a.result = result;
+    return rc_of(lzf_launch_store_mlock(a, (hipStream_t)stream));
 }
 
 int lzf_gpu_store_munlock(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
@@ -1026,15 +1024,14 @@ int lzf_gpu_store_munlock(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_
                           int64_t *last_access, uint8_t *entry_status, uint64_t *result, void *stream)
 {
     if (!idx || !enc || !item_time || !item_ttl || !item_lock || !result || !n || !count) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfLockArgs a{};
-    a.idx = idx; a.n = n; a.enc = enc; a.count = count;
-    a.item_time = const_cast<int64_t *>(item_time);        /* MUNLOCK only reads it */
-    a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
-    a.last_access = last_access; a.entry_status = entry_status; a.result = result;
-    const hipError_t e = lzf_launch_store_munlock(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    a.idx = idx; a.n = n;
+    /* MUNLOCK only reads the time arrays */
+    a.it = items_of(enc, count, const_cast<int64_t *>(item_time), const_cast<int32_t *>(item_ttl), item_lock,
+                    last_access, now);
+    a.entry_status = entry_status; a.result = result;
+    return rc_of(lzf_launch_store_munlock(a, (hipStream_t)stream));
 }
 
 int lzf_gpu_store_mdel(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
@@ -1043,15 +1040,14 @@ int lzf_gpu_store_mdel(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t c
 {
     if (!idx || !enc || !result || !n || !count) return LZF_GPU_EARG;
     if (!item_time != !item_ttl || (item_lock && !item_time)) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfLockArgs a{};
-    a.idx = idx; a.n = n; a.enc = enc; a.count = count;
-    a.item_time = const_cast<int64_t *>(item_time);        /* MDEL reads the time arrays only */
-    a.item_ttl = item_ttl; a.item_lock = const_cast<int64_t *>(item_lock); a.now = now;
+    a.idx = idx; a.n = n;
+    /* MDEL reads the time arrays and the locks only */
+    a.it = items_of(enc, count, const_cast<int64_t *>(item_time), const_cast<int32_t *>(item_ttl),
+                    const_cast<int64_t *>(item_lock), nullptr, now);
     a.entry_status = entry_status; a.result = result;
-    const hipError_t e = lzf_launch_store_mdel(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_mdel(a, (hipStream_t)stream));
 }
 
 uint64_t lzf_gpu_store_minc_work_size(uint32_t n)
@@ -1069,18 +1065,18 @@ int lzf_gpu_store_minc(const uint32_t *idx, uint32_t n, int64_t delta, int singl
     if (!idx || !store || !store_used || !val_off || !val_size || !enc || !result || !status || !work)
         return LZF_GPU_EARG;
     if (!n || !count || !item_time != !item_ttl || (item_lock && !item_time)) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfMincArgs a{};
     a.idx = idx; a.n = n; a.delta = delta; a.single = single ? 1 : 0;
     a.store = store; a.store_cap = store_cap; a.store_used = store_used;
-    a.val_off = val_off; a.val_size = val_size; a.enc = enc; a.count = count;
-    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
-    a.last_access = last_access; a.entry_status = entry_status; a.entry_value = entry_value;
+    a.val_off = val_off; a.val_size = val_size;
+    /* INC / DEC read the time arrays and the locks only */
+    a.it = items_of(enc, count, const_cast<int64_t *>(item_time), const_cast<int32_t *>(item_ttl),
+                    const_cast<int64_t *>(item_lock), last_access, now);
+    a.entry_status = entry_status; a.entry_value = entry_value;
     a.result = result; a.status = status;
     lzf_minc_carve(a, work);
-    const hipError_t e = lzf_launch_store_minc(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_minc(a, (hipStream_t)stream));
 }
 
 int lzf_host_parse_long(const uint8_t *v, uint32_t len, int64_t *out)
@@ -1095,11 +1091,11 @@ int lzf_gpu_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, uin
 {
     if (!occ || !enc || !item_time || !item_lock || !result) return LZF_GPU_EARG;
     if (!count || !n || (uint64_t)first + n > count) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
-    const hipError_t e = lzf_launch_store_set_guard(occ, first, n, enc, count, item_time, item_lock, now, refused,
-                                                    result, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    if (const int rc = current_device_ok()) return rc;
+    /* the guard reads the times and the locks only */
+    const LzfItems it = items_of(enc, count, const_cast<int64_t *>(item_time), nullptr, const_cast<int64_t *>(item_lock),
+                                 nullptr, now);
+    return rc_of(lzf_launch_store_set_guard(occ, first, n, it, refused, result, (hipStream_t)stream));
 }
 
 uint64_t lzf_gpu_store_mset_work_size(uint32_t n, uint32_t vlen)
@@ -1119,17 +1115,15 @@ int lzf_gpu_store_mset(const uint32_t *idx, uint32_t n, const uint8_t *value, ui
         return LZF_GPU_EARG;
     if (!n || !count || !store_cap) return LZF_GPU_EARG;
     if (!vlen || vlen > LZF_GPU_MAX_VALUE) return LZF_GPU_EARG;   /* the reference asserts vlen > 0 */
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfMsetArgs a{};
     a.idx = idx; a.n = n; a.value = value; a.vlen = vlen; a.compression = compression;
     a.store = store; a.store_cap = store_cap; a.store_used = store_used;
-    a.val_off = val_off; a.val_size = val_size; a.enc = enc; a.val_len = val_len; a.count = count;
-    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
-    a.last_access = last_access; a.entry_status = entry_status; a.result = result; a.status = status;
+    a.val_off = val_off; a.val_size = val_size; a.val_len = val_len;
+    a.it = items_of(enc, count, item_time, item_ttl, item_lock, last_access, now);
+    a.entry_status = entry_status; a.result = result; a.status = status;
     lzf_mset_carve(a, work);
-    const hipError_t e = lzf_launch_store_mset(a, (hipStream_t)stream, store_compress);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_mset(a, (hipStream_t)stream, store_compress));
 }
 
 int lzf_gpu_store_gc(const int64_t *last_access, int64_t now, int64_t gc_ratio,
@@ -1137,11 +1131,10 @@ int lzf_gpu_store_gc(const int64_t *last_access, int64_t now, int64_t gc_ratio,
                      const uint64_t *gate, uint64_t max_bytes, uint64_t *result, void *stream)
 {
     if (!last_access || !enc || !val_size || !result || !count) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
-    const hipError_t e = lzf_launch_store_gc(last_access, now, gc_ratio, enc, val_size, count, gate, max_bytes,
-                                             result, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    if (const int rc = current_device_ok()) return rc;
+    /* the sweep only reads last_access */
+    const LzfItems it = items_of(enc, count, nullptr, nullptr, nullptr, const_cast<int64_t *>(last_access), now);
+    return rc_of(lzf_launch_store_gc(it, gc_ratio, val_size, gate, max_bytes, result, (hipStream_t)stream));
 }
 
 int lzf_host_meta_field(const uint8_t *m, uint32_t mlen)
@@ -1157,14 +1150,14 @@ int lzf_gpu_store_meta(const uint32_t *idx, uint32_t n, int field, uint8_t *enc,
     if (!idx || !enc || !val_size || !item_time || !item_ttl || !entry_value || !result) return LZF_GPU_EARG;
     if (!n || !count || field < LZF_META_SIZE || field > LZF_META_LOCK) return LZF_GPU_EARG;
     if (field == LZF_META_ACCESS && !last_access) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfMetaArgs a{};
-    a.idx = idx; a.n = n; a.field = field; a.enc = enc; a.val_size = val_size; a.count = count;
-    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.now = now;
-    a.last_access = last_access; a.entry_status = entry_status; a.entry_value = entry_value; a.result = result;
-    const hipError_t e = lzf_launch_store_meta(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    a.idx = idx; a.n = n; a.field = field; a.val_size = val_size;
+    /* META reads the time arrays and the locks only */
+    a.it = items_of(enc, count, const_cast<int64_t *>(item_time), const_cast<int32_t *>(item_ttl),
+                    const_cast<int64_t *>(item_lock), last_access, now);
+    a.entry_status = entry_status; a.entry_value = entry_value; a.result = result;
+    return rc_of(lzf_launch_store_meta(a, (hipStream_t)stream));
 }
 
 uint64_t lzf_gpu_store_keys_work_size(uint32_t n)
@@ -1181,15 +1174,13 @@ int lzf_gpu_store_keys(const uint32_t *idx, uint32_t n,
     if (!idx || !keys || !key_off || !key_len || !enc || !frame || !frame_len || !result || !work)
         return LZF_GPU_EARG;
     if (!n || !count) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfKeysArgs a{};
     a.idx = idx; a.n = n; a.keys = keys; a.key_off = key_off; a.key_len = key_len; a.enc = enc; a.count = count;
     a.reply_header = reply_header;
     a.frame = frame; a.max_response = max_response; a.frame_len = frame_len; a.result = result;
     lzf_keys_carve(a, work);
-    const hipError_t e = lzf_launch_store_keys(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_store_keys(a, (hipStream_t)stream));
 }
 
 uint64_t lzf_gpu_key_index_bytes(uint32_t slots)
@@ -1211,15 +1202,13 @@ int lzf_gpu_key_index_insert(void *table, uint32_t slots, uint32_t *used,
     if (!table || !used || !keys || !key_off || !key_len || !enc || !result || !status) return LZF_GPU_EARG;
     if (!count || !n || (uint64_t)first + n > count) return LZF_GPU_EARG;
     if (!lzf_kidx_slots_ok(slots) || ((uintptr_t)table & 7u)) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfKidxArgs a{};
     a.table = table; a.slots = slots; a.used = used;
     a.keys = keys; a.key_off = key_off; a.key_len = key_len;
     a.enc = enc; a.count = count; a.first = first; a.n = n;
     a.result = result; a.status = status;
-    const hipError_t e = lzf_launch_kidx_insert(a, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_kidx_insert(a, (hipStream_t)stream));
 }
 
 int lzf_gpu_key_index_lookup(const void *table, uint32_t slots,
@@ -1232,15 +1221,13 @@ int lzf_gpu_key_index_lookup(const void *table, uint32_t slots,
         return LZF_GPU_EARG;
     if (!count || !nq) return LZF_GPU_EARG;
     if (!lzf_kidx_slots_ok(slots) || ((uintptr_t)table & 7u)) return LZF_GPU_EARG;
-    int rc = current_device_ok();
-    if (rc) return rc;
+    if (const int rc = current_device_ok()) return rc;
     LzfKidxArgs a{};
     a.table = const_cast<void *>(table); a.slots = slots;  /* the lookup only reads */
     a.keys = keys; a.key_off = key_off; a.key_len = key_len;
     a.enc = const_cast<uint8_t *>(enc); a.count = count;
     a.result = result;
-    const hipError_t e = lzf_launch_kidx_lookup(a, qkeys, q_off, q_len, nq, idx, (hipStream_t)stream);
-    return e == hipSuccess ? LZF_GPU_OK : code_of(e);
+    return rc_of(lzf_launch_kidx_lookup(a, qkeys, q_off, q_len, nq, idx, (hipStream_t)stream));
 }
 
 int lzf_gpu_selfcheck(void)

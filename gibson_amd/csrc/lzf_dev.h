@@ -1,12 +1,9 @@
 /*
  * lzf_dev.h -- device helpers shared by the compress kernels (lzf_cand.hip):
  * unaligned byte-window loads that never touch memory past a value's end,
- * and the reference's slot function; and the block-wide scan of the store's
- * kernels (lzf_store.hip, lzf_mget.hip) with the carry scan over tile sums
- * (lzf_mset.hip, lzf_meta.hip); and the per-item rules the index-list
- * operators share (lzf_mget.hip, lzf_ops.hip, lzf_mset.hip, lzf_meta.hip):
- * validity, lock, number parse; and the size-class rule (lzf_mixed.hip,
- * lzf_reply.hip) and the reply code of an entry status (lzf_reply.hip).
+ * and the reference's slot function; and the size-class rule of the mixed-size
+ * batches (lzf_mixed.hip), which the reply kernels share.  The store's kernels
+ * take all of it through their own toolkit, lzf_store_dev.h.
  */
 #ifndef GIBSON_AMD_LZF_DEV_H
 #define GIBSON_AMD_LZF_DEV_H
@@ -141,130 +138,13 @@ __device__ __forceinline__ void dv_st_exact(uint8_t *p, uint4 v, uint32_t len)
     if (len & 1u) *p = (uint8_t)a;
 }
 
-__device__ inline uint64_t dv_shfl_up64(uint64_t x, int d)
-{
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, d, 64);
-    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-/* block-wide exclusive scan of one u64 per thread (the scans of lzf_store.hip
- * and lzf_mget.hip), for a workgroup of WAVES waves: an inclusive wave scan,
- * then the totals of the waves before this one; sw: WAVES words of LDS */
-template <uint32_t WAVES>
-__device__ inline uint64_t dv_block_excl(uint64_t x, uint64_t *sw, uint64_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = dv_shfl_up64(inc, d);
-        if (lane >= (uint32_t)d) inc += o;
-    }
-    if (lane == 63u) sw[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0ull, all = 0ull;
-    for (uint32_t w = 0; w < WAVES; w++) {
-        if (w < wave) before += sw[w];
-        all += sw[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + inc - x;
-}
-
-/* one workgroup of WAVES waves: the exclusive scan of the n sums at v in place,
- * in pieces of 64 * WAVES * DV_CARRY_PER with a running carry, a thread taking
- * DV_CARRY_PER neighbouring sums (the carry step between a per-tile reduce and
- * a per-tile write, lzf_mset.hip, lzf_meta.hip); the total, in every thread */
-#define DV_CARRY_PER 8u
-template <uint32_t WAVES>
-__device__ inline uint64_t dv_carry_scan(uint64_t *v, uint32_t n, uint64_t *sw)
-{
-    uint64_t run = 0ull;
-    for (uint64_t c = 0; c < n; c += 64u * WAVES * DV_CARRY_PER) {
-        const uint64_t first = c + threadIdx.x * DV_CARRY_PER;
-        uint64_t x[DV_CARRY_PER], s = 0ull;
-#pragma unroll
-        for (uint32_t j = 0; j < DV_CARRY_PER; j++) {
-            x[j] = first + j < n ? v[first + j] : 0ull;
-            s += x[j];
-        }
-        uint64_t tot;
-        uint64_t o = run + dv_block_excl<WAVES>(s, sw, &tot);
-#pragma unroll
-        for (uint32_t j = 0; j < DV_CARRY_PER; j++) {
-            if (first + j < n) v[first + j] = o;
-            o += x[j];
-        }
-        run += tot;
-    }
-    return run;
-}
-
-enum { MG_DEAD = 0, MG_EXPIRED = 1, MG_VALID = 2 };
-
-/* The validity rule of every index-list operator (gbIsItemStillValid,
- * src/query.c:204-224, over the rule of src/query.c:186-189): entry i is dead
- * when it is out of range or already NULL, expired when its ttl is positive
- * and reached -- the caller then nulls enc[i], the device form of tr_remove --
- * and valid otherwise.  No time arrays: nothing expires */
-__device__ inline int mg_validity(uint32_t i, uint32_t count, const uint8_t *enc, const int64_t *item_time,
-                                  const int32_t *item_ttl, int64_t now)
-{
-    if (i >= count || enc[i] == (uint8_t)LZF_ENC_NULL) return MG_DEAD;
-    if (item_ttl) {
-        const int32_t t = item_ttl[i];
-        /* now - time in two's complement, as the reference's time_t arithmetic wraps */
-        const int64_t age = (int64_t)((uint64_t)now - (uint64_t)item_time[i]);
-        if (t > 0 && age >= (int64_t)t) return MG_EXPIRED;
-    }
-    return MG_VALID;
-}
-
-/* The lock rule (gbItemIsLocked, src/query.c:171-178) for an in-range item i:
- * locked for good at -1, otherwise while now - time is below the lock time.
- * No lock array: nothing is locked */
-__device__ inline bool mg_locked(uint32_t i, const int64_t *item_time, const int64_t *item_lock, int64_t now)
-{
-    if (!item_lock) return false;
-    const int64_t lock = item_lock[i];
-    const int64_t age = (int64_t)((uint64_t)now - (uint64_t)item_time[i]);
-    return lock == -1 || age < lock;
-}
-
-/* gbQueryParseLong (src/query.c:39-76), quirk for quirk: a first byte '0'
- * yields 0 whatever follows; a leading '-' negates and a lone "-" is 0; every
- * other byte must be a digit; no length limit, the accumulation n * 10 + d and
- * the negation modulo 2^64 (what the reference's x86-64 build computes where C
- * leaves the signed overflow undefined).  len == 0: not a number (the
- * reference asserts vlen > 0) */
-__host__ __device__ inline int lzf_parse_long(const uint8_t *v, uint32_t len, int64_t *out)
-{
-    if (!len) return 0;
-    if (v[0] == (uint8_t)'0') {
-        *out = 0;
-        return 1;
-    }
-    const uint32_t neg = v[0] == (uint8_t)'-' ? 1u : 0u;
-    uint64_t n = 0ull;
-    for (uint32_t i = neg; i < len; i++) {
-        const uint32_t d = (uint32_t)v[i] - (uint32_t)'0';
-        if (d > 9u) return 0;
-        n = n * 10ull + d;
-    }
-    *out = (int64_t)(neg ? 0ull - n : n);
-    return 1;
-}
-
 /* The size classes.  Compress, by in_len: the edges of the routing's value
  * sizes (lane_min_count and LANE_DEFAULT_MAX of lzf_api.cpp; window64 past
  * 64 KiB).  Decompress, by out_cap: tokpar64 up to 4 KiB, tokpar64-far up to
  * CD_FAR_MAX (16 KiB), the pipe past it (lzf_launch_decompress).  A length
  * past the caller's bound is refused: class LZF_GPU_NCLASS.  The only place
- * the edges are written: lzf_decode_class_edge names the decode ones. */
-#define LZF_DECODE_NCLASS 3u
-#define LZF_DECODE_EDGE0  4096u
-#define LZF_DECODE_EDGE1  16384u
+ * the edges are used: LZF_DECODE_EDGE* (lzf_internal.h) and
+ * lzf_decode_class_edge name the decode ones. */
 static __host__ __device__ inline uint32_t lzf_size_class_of(uint32_t len, uint32_t bound, int kind)
 {
     if (len > bound) return (uint32_t)LZF_GPU_NCLASS;
@@ -277,24 +157,6 @@ static __host__ __device__ inline uint32_t lzf_size_class_of(uint32_t len, uint3
 static inline uint32_t lzf_decode_class_edge(uint32_t c)
 {
     return c == 0u ? LZF_DECODE_EDGE0 : c == 1u ? LZF_DECODE_EDGE1 : 0xFFFFFFFFu;
-}
-
-/* The reply code of an operator's entry status, the single-key replies of
- * gbQueryIncDecHandler and its kin (src/query.c:853-886): REPL_VAL for an
- * entry the operator applied to, the error code of the others.  One rule for
- * the reply kernels and lzf_host_reply_code */
-__host__ __device__ inline int lzf_reply_code_of(int ent_status)
-{
-    switch (ent_status) {
-    case LZF_ENT_DONE:
-    case LZF_ENT_CONVERTED: return LZF_REPL_VAL;
-    case LZF_ENT_DEAD:
-    case LZF_ENT_EXPIRED: return LZF_REPL_ERR_NOT_FOUND;
-    case LZF_ENT_LOCKED: return LZF_REPL_ERR_LOCKED;
-    case LZF_ENT_NAN:
-    case LZF_ENT_UNCHANGED: return LZF_REPL_ERR_NAN;
-    default: return LZF_REPL_ERR;
-    }
 }
 
 #endif

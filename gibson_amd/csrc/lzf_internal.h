@@ -30,6 +30,29 @@ struct LzfBatch {
     const uint8_t *skip;   /* decompress: values with skip[i] != 0 are left alone (NULL: none) */
 };
 
+/* the store's item arrays as one view, device pointers: what every index-list
+ * operator and sweep reads and writes of an item besides its value.  A NULL
+ * member means what it meant as a loose argument: no time arrays (item_time
+ * and item_ttl NULL together), nothing expires; no item_lock, nothing is
+ * locked; no last_access, none is kept.  The members are not const, as some
+ * operator writes each of them; an operator that only reads an array says so
+ * where its view is built (lzf_api.cpp) */
+struct LzfItems {
+    uint8_t *enc;
+    uint32_t count;
+    int64_t *item_time;
+    int32_t *item_ttl;
+    int64_t *item_lock;
+    int64_t *last_access;
+    int64_t now;
+};
+
+/* the decode size classes (the rule: lzf_size_class_of, lzf_dev.h); here
+ * because the reply work area holds one skip list per class */
+#define LZF_DECODE_NCLASS 3u
+#define LZF_DECODE_EDGE0  4096u
+#define LZF_DECODE_EDGE1  16384u
+
 /* the MGET reply frame (lzf_frame.hip); device pointers */
 struct LzfFrameArgs {
     const uint8_t *keys;
@@ -46,7 +69,7 @@ struct LzfFrameArgs {
     uint64_t max_response;
     uint8_t *frame;
     uint64_t *frame_len;
-    /* work area (lzf_frame_carve) */
+    /* work area (lzf_frame_layout, lzf_store_layout.h) */
     uint64_t *w_off, *w_voff, *w_bsum, *w_state;
     uint32_t *w_len;
     int32_t *w_err;
@@ -67,7 +90,7 @@ struct LzfStoreArgs {
     uint32_t *val_size;
     uint8_t *enc;
     uint32_t *status;
-    /* work area (lzf_store_carve) */
+    /* work area (lzf_store_layout) */
     uint64_t *w_state, *w_slot_off, *w_tile;
     uint32_t *w_len, *w_cap, *w_out;
     uint8_t *w_slots;
@@ -87,7 +110,7 @@ struct LzfCompactArgs {
     uint64_t *dst_used;
     uint64_t *report;
     uint32_t *status;
-    /* work area (lzf_compact_carve): per scan tile the live count (top bit: a
+    /* work area (lzf_compact_layout): per scan tile the live count (top bit: a
      * live item out of range), the live bytes and the dead bytes; the dense
      * list of the live items, destination and source offset per live rank */
     uint64_t *w_state, *w_tile_n, *w_tile_b, *w_tile_d, *w_live_dst, *w_live_src;
@@ -105,7 +128,7 @@ struct LzfSelectArgs {
     uint32_t *sel;
     uint32_t cap;
     uint32_t *result;
-    /* work area (lzf_select_carve): one 64-bit match word per 64 items, and
+    /* work area (lzf_select_layout): one 64-bit match word per 64 items, and
      * per tile its match count, then the matches before it */
     uint64_t *w_mask, *w_tile;
 };
@@ -120,20 +143,15 @@ struct LzfMgetArgs {
     const uint8_t *store;
     const uint64_t *val_off;
     const uint32_t *val_size;
-    uint8_t *enc;
     const uint32_t *val_len;
-    uint32_t count;
-    const int64_t *item_time;
-    const int32_t *item_ttl;
-    int64_t now;
-    int64_t *last_access;
+    LzfItems it;
     uint32_t max_val_len;
     int reply_header;
     uint8_t *frame;
     uint64_t max_response;
     uint64_t *frame_len;
     uint64_t *result;
-    /* work area (lzf_mget_carve).  g_*: the entries' descriptors in list order
+    /* work area (lzf_mget_layout).  g_*: the entries' descriptors in list order
      * (a dropped entry: g_enc NULL; g_null: the item an expired entry nulls);
      * w_*: as LzfFrameArgs, and per tile the frame bytes and the three counts */
     uint64_t *w_state, *g_key_off, *g_val_off, *w_off, *w_voff, *w_tile, *w_tcnt;
@@ -152,13 +170,8 @@ struct LzfReplyArgs {
     const uint8_t *store;
     const uint64_t *val_off;
     const uint32_t *val_size;
-    uint8_t *enc;
     const uint32_t *val_len;
-    uint32_t count;
-    const int64_t *item_time;
-    const int32_t *item_ttl;
-    int64_t now;
-    int64_t *last_access;
+    LzfItems it;
     uint32_t max_val_len;
     uint8_t *replies;
     uint64_t rep_cap;
@@ -167,7 +180,7 @@ struct LzfReplyArgs {
     uint32_t *rep_len;
     uint8_t *entry_status;
     uint64_t *result;
-    /* work area (lzf_reply_carve).  g_*: the entries' descriptors in list order
+    /* work area (lzf_reply_layout).  g_*: the entries' descriptors in list order
      * (g_code: the entry's LZF_REPL_* code; g_cls: its decode class, RP_NO_CLASS
      * when the decoder has nothing to do for it; g_null: the item an expired
      * entry nulls); w_off: the slot's offset inside its tile; per tile the slot
@@ -196,19 +209,13 @@ struct LzfKidxArgs {
 };
 
 /* the lock operators over an index list (lzf_ops.hip); device pointers.
- * lock_time: MLOCK only; item_ttl / item_lock / last_access / entry_status
- * may be NULL where the call allows it */
+ * lock_time: MLOCK only; the view's item_ttl / item_lock / last_access and
+ * entry_status may be NULL where the call allows it */
 struct LzfLockArgs {
     const uint32_t *idx;
     uint32_t n;
     int64_t lock_time;
-    uint8_t *enc;
-    uint32_t count;
-    int64_t *item_time;
-    const int32_t *item_ttl;
-    int64_t *item_lock;
-    int64_t now;
-    int64_t *last_access;
+    LzfItems it;
     uint8_t *entry_status;
     uint64_t *result;
 };
@@ -224,18 +231,12 @@ struct LzfMincArgs {
     uint64_t *store_used;
     uint64_t *val_off;
     uint32_t *val_size;
-    uint8_t *enc;
-    uint32_t count;
-    const int64_t *item_time;
-    const int32_t *item_ttl;
-    const int64_t *item_lock;
-    int64_t now;
-    int64_t *last_access;
+    LzfItems it;
     uint8_t *entry_status;
     int64_t *entry_value;
     uint64_t *result;
     uint32_t *status;
-    /* work area (lzf_minc_carve): the call's base and status; per entry its
+    /* work area (lzf_minc_layout): the call's base and status; per entry its
      * new number and its LZF_ENT_* class; per tile its converted entries, then
      * the converted entries before it */
     uint64_t *w_state, *w_tile;
@@ -254,18 +255,12 @@ struct LzfMsetArgs {
     uint64_t *store_used;
     uint64_t *val_off;
     uint32_t *val_size;
-    uint8_t *enc;
     uint32_t *val_len;
-    uint32_t count;
-    int64_t *item_time;
-    int32_t *item_ttl;
-    int64_t *item_lock;
-    int64_t now;
-    int64_t *last_access;
+    LzfItems it;
     uint8_t *entry_status;
     uint64_t *result;
     uint32_t *status;
-    /* work area (lzf_mset_carve): the call's base, status and stored form; the
+    /* work area (lzf_mset_layout): the call's base, status and stored form; the
      * descriptors of the one-value compress batch (c_off: in_off, out_off;
      * c_len: in_len, out_cap, out_len); per tile its DONE entries, then the
      * DONE entries before it; per entry its LZF_ENT_* class; the compress slot */
@@ -279,14 +274,8 @@ struct LzfMetaArgs {
     const uint32_t *idx;
     uint32_t n;
     int field;
-    uint8_t *enc;
     const uint32_t *val_size;
-    uint32_t count;
-    const int64_t *item_time;
-    const int32_t *item_ttl;
-    const int64_t *item_lock;
-    int64_t now;
-    int64_t *last_access;
+    LzfItems it;
     uint8_t *entry_status;
     int64_t *entry_value;
     uint64_t *result;
@@ -306,7 +295,7 @@ struct LzfKeysArgs {
     uint64_t max_response;
     uint64_t *frame_len;
     uint64_t *result;
-    /* work area (lzf_keys_carve): found, payload, status; per tile its
+    /* work area (lzf_keys_layout): found, payload, status; per tile its
      * participating entries and their key bytes, then those before it */
     uint64_t *w_state, *w_tile_n, *w_tile_b;
 };
@@ -339,7 +328,9 @@ struct LzfParts {
     const hipEvent_t *ev;
 };
 
-/* launchers, defined next to their kernels; return hipSuccess or the error */
+/* launchers, defined next to their kernels; return hipSuccess or the error.
+ * The store's lzf_X_work_bytes / lzf_X_carve pairs are defined together in
+ * lzf_layout.cpp, each pair from the one layout of lzf_store_layout.h */
 hipError_t lzf_launch_compress_table(const LzfBatch &b, hipStream_t s, void *scratch, size_t scratch_bytes,
                                      uint32_t *chunks, const LzfParts *parts = nullptr);
 size_t lzf_table_scratch_per_value(uint32_t max_len);
@@ -379,8 +370,7 @@ void lzf_store_carve(LzfStoreArgs &a, void *work);
 /* the store's lifecycle (lzf_store.hip): items nulled by index and by TTL,
  * the usage report, and the compaction of the live items into a second arena */
 hipError_t lzf_launch_store_delete(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count, hipStream_t s);
-hipError_t lzf_launch_store_expire(const int64_t *item_time, const int32_t *ttl, int64_t now, uint8_t *enc,
-                                   uint32_t count, uint32_t *expired, hipStream_t s);
+hipError_t lzf_launch_store_expire(const LzfItems &it, uint32_t *expired, hipStream_t s);
 hipError_t lzf_launch_store_usage(LzfCompactArgs &a, hipStream_t s);
 hipError_t lzf_launch_store_compact(LzfCompactArgs &a, hipStream_t s);
 uint64_t lzf_compact_work_bytes(uint32_t count);
@@ -394,12 +384,10 @@ void lzf_select_carve(LzfSelectArgs &a, void *work);
 hipError_t lzf_launch_store_mget(LzfMgetArgs &a, hipStream_t s, hipError_t (*decode)(const LzfBatch &, hipStream_t));
 uint64_t lzf_mget_work_bytes(uint32_t n);
 void lzf_mget_carve(LzfMgetArgs &a, void *work);
-hipError_t lzf_launch_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
-                                  const int64_t *item_time, const int32_t *item_ttl, int64_t now, int64_t *last_access,
-                                  uint64_t *result, hipStream_t s);
-hipError_t lzf_launch_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, uint8_t *enc, uint32_t count,
-                                 int64_t *item_time, int32_t *item_ttl, int64_t now, int64_t *last_access,
-                                 uint64_t *result, hipStream_t s);
+hipError_t lzf_launch_store_count(const uint32_t *idx, uint32_t n, const LzfItems &it, uint64_t *result,
+                                  hipStream_t s);
+hipError_t lzf_launch_store_mttl(const uint32_t *idx, uint32_t n, int32_t ttl, const LzfItems &it, uint64_t *result,
+                                 hipStream_t s);
 /* one reply frame per entry of an index list (lzf_reply.hip): classify, scan,
  * write, `decode` once per decode size class (one_route: once, with
  * max_val_len) over the gathered entries, in place in the arena, check; and
@@ -418,8 +406,7 @@ hipError_t lzf_launch_store_mdel(const LzfLockArgs &a, hipStream_t s);
 hipError_t lzf_launch_store_minc(LzfMincArgs &a, hipStream_t s);
 uint64_t lzf_minc_work_bytes(uint32_t n);
 void lzf_minc_carve(LzfMincArgs &a, void *work);
-hipError_t lzf_launch_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, uint8_t *enc, uint32_t count,
-                                      const int64_t *item_time, const int64_t *item_lock, int64_t now,
+hipError_t lzf_launch_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, const LzfItems &it,
                                       uint8_t *refused, uint64_t *result, hipStream_t s);
 int lzf_ops_parse_long(const uint8_t *v, uint32_t len, int64_t *out);
 /* MSET over an index list (lzf_mset.hip): classify, `compress` over the one
@@ -430,9 +417,8 @@ uint64_t lzf_mset_work_bytes(uint32_t n, uint32_t vlen);
 void lzf_mset_carve(LzfMsetArgs &a, void *work);
 /* the memory sweep, META and the KEYS frame (lzf_meta.hip), and META's field
  * name on the host */
-hipError_t lzf_launch_store_gc(const int64_t *last_access, int64_t now, int64_t gc_ratio, uint8_t *enc,
-                               const uint32_t *val_size, uint32_t count, const uint64_t *gate, uint64_t max_bytes,
-                               uint64_t *result, hipStream_t s);
+hipError_t lzf_launch_store_gc(const LzfItems &it, int64_t gc_ratio, const uint32_t *val_size, const uint64_t *gate,
+                               uint64_t max_bytes, uint64_t *result, hipStream_t s);
 hipError_t lzf_launch_store_meta(const LzfMetaArgs &a, hipStream_t s);
 int lzf_meta_field(const uint8_t *m, uint32_t mlen);
 hipError_t lzf_launch_store_keys(LzfKeysArgs &a, hipStream_t s);

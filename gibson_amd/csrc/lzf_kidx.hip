@@ -41,11 +41,10 @@
  * The kernels are helpers of this translation unit, not part of the library's
  * routed kernel set: they have internal linkage (anonymous namespace).
  */
-#include "lzf_dev.h"
+#include "lzf_store_dev.h"
 #include "../../include/lzf_gpu.h"
 
-#define KI_BLOCK 256u
-#define KI_GRID  2048u                    /* grid-stride kernels: 256 CUs x 8 workgroups */
+/* the grid-stride geometry and the wave sum: lzf_store_dev.h */
 #define KI_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define KI_MISS  0xFFFFFFFFu
 
@@ -150,21 +149,16 @@ __device__ inline bool ki_same_key(const uint8_t *a, const uint8_t *b, uint32_t 
  * (profiles/r11/kidx/) */
 __device__ inline bool ki_block_sums(uint64_t (&v)[3])
 {
-    __shared__ uint64_t sh[3][KI_BLOCK / 64u];
+    __shared__ uint64_t sh[3][SD_WAVES];
     for (uint32_t c = 0; c < 3u; c++) {
-        uint64_t x = v[c];
-        for (int d = 32; d; d >>= 1) {
-            const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)x, d, 64);
-            const uint32_t hi = (uint32_t)__shfl_down((int)(uint32_t)(x >> 32), d, 64);
-            x += ((uint64_t)hi << 32) | lo;
-        }
+        const uint64_t x = sd_wave_sum(v[c]);
         if ((threadIdx.x & 63u) == 0u) sh[c][threadIdx.x >> 6] = x;
     }
     __syncthreads();
     if (threadIdx.x != 0u) return false;
     for (uint32_t c = 0; c < 3u; c++) {
         v[c] = 0ull;
-        for (uint32_t w = 0; w < KI_BLOCK / 64u; w++) v[c] += sh[c][w];
+        for (uint32_t w = 0; w < SD_WAVES; w++) v[c] += sh[c][w];
     }
     return true;
 }
@@ -182,14 +176,14 @@ __global__ void lzf_kidx_decide_kernel(LzfKidxArgs a)
     a.result[0] = a.result[1] = a.result[2] = a.result[3] = 0ull;
 }
 
-__global__ __launch_bounds__(KI_BLOCK) void lzf_kidx_claim_kernel(LzfKidxArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_kidx_claim_kernel(LzfKidxArgs a)
 {
     if (*a.status != (uint32_t)LZF_KIDX_OK) return;
     unsigned long long *table = (unsigned long long *)a.table;
     const uint32_t mask = a.slots - 1u;
-    const uint64_t step = (uint64_t)gridDim.x * KI_BLOCK;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint32_t claimed = 0u, replaced = 0u;
-    for (uint64_t k = (uint64_t)blockIdx.x * KI_BLOCK + threadIdx.x; k < a.n; k += step) {
+    for (uint64_t k = (uint64_t)blockIdx.x * SD_BLOCK + threadIdx.x; k < a.n; k += step) {
         const uint32_t i = a.first + (uint32_t)k, len = a.key_len[i];
         if (a.enc[i] == (uint8_t)LZF_ENC_NULL || !len) continue;
         const uint8_t *key = a.keys + a.key_off[i];
@@ -243,14 +237,14 @@ __global__ __launch_bounds__(KI_BLOCK) void lzf_kidx_claim_kernel(LzfKidxArgs a)
     if (v[1]) atomicAdd((unsigned long long *)&a.result[1], (unsigned long long)v[1]);
 }
 
-__global__ __launch_bounds__(KI_BLOCK) void lzf_kidx_settle_kernel(LzfKidxArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_kidx_settle_kernel(LzfKidxArgs a)
 {
     if (*a.status != (uint32_t)LZF_KIDX_OK) return;
     const uint64_t *table = (const uint64_t *)a.table;
     const uint32_t mask = a.slots - 1u;
-    const uint64_t step = (uint64_t)gridDim.x * KI_BLOCK;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint32_t mapped = 0u, superseded = 0u, skipped = 0u;
-    for (uint64_t k = (uint64_t)blockIdx.x * KI_BLOCK + threadIdx.x; k < a.n; k += step) {
+    for (uint64_t k = (uint64_t)blockIdx.x * SD_BLOCK + threadIdx.x; k < a.n; k += step) {
         const uint32_t i = a.first + (uint32_t)k, len = a.key_len[i];
         if (a.enc[i] == (uint8_t)LZF_ENC_NULL || !len) {
             skipped++;
@@ -283,16 +277,16 @@ __global__ __launch_bounds__(KI_BLOCK) void lzf_kidx_settle_kernel(LzfKidxArgs a
 }
 
 /* result[] was zeroed on the stream before the launch */
-__global__ __launch_bounds__(KI_BLOCK) void lzf_kidx_lookup_kernel(LzfKidxArgs a, const uint8_t *__restrict__ qkeys,
+__global__ __launch_bounds__(SD_BLOCK) void lzf_kidx_lookup_kernel(LzfKidxArgs a, const uint8_t *__restrict__ qkeys,
                                                                    const uint64_t *__restrict__ q_off,
                                                                    const uint32_t *__restrict__ q_len, uint32_t nq,
                                                                    uint32_t *__restrict__ idx)
 {
     const uint64_t *table = (const uint64_t *)a.table;
     const uint32_t mask = a.slots - 1u;
-    const uint64_t step = (uint64_t)gridDim.x * KI_BLOCK;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint64_t hits = 0ull, misses = 0ull, examined = 0ull;
-    for (uint64_t k = (uint64_t)blockIdx.x * KI_BLOCK + threadIdx.x; k < nq; k += step) {
+    for (uint64_t k = (uint64_t)blockIdx.x * SD_BLOCK + threadIdx.x; k < nq; k += step) {
         const uint32_t len = q_len[k];
         uint32_t found = KI_MISS;
         if (len) {
@@ -323,12 +317,6 @@ __global__ __launch_bounds__(KI_BLOCK) void lzf_kidx_lookup_kernel(LzfKidxArgs a
     if (v[2]) atomicAdd((unsigned long long *)&a.result[2], (unsigned long long)v[2]);
 }
 
-inline uint32_t ki_grid(uint64_t n)
-{
-    const uint64_t g = (n + KI_BLOCK - 1u) / KI_BLOCK;
-    return (uint32_t)(g < KI_GRID ? g : KI_GRID);
-}
-
 }  // namespace
 
 bool lzf_kidx_slots_ok(uint32_t slots)
@@ -346,8 +334,8 @@ uint32_t lzf_kidx_home(const uint8_t *key, uint32_t len, uint32_t slots)
 hipError_t lzf_launch_kidx_insert(LzfKidxArgs &a, hipStream_t s)
 {
     hipLaunchKernelGGL(lzf_kidx_decide_kernel, dim3(1), dim3(1), 0, s, a);
-    hipLaunchKernelGGL(lzf_kidx_claim_kernel, dim3(ki_grid(a.n)), dim3(KI_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(lzf_kidx_settle_kernel, dim3(ki_grid(a.n)), dim3(KI_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_kidx_claim_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_kidx_settle_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
@@ -356,6 +344,6 @@ hipError_t lzf_launch_kidx_lookup(LzfKidxArgs &a, const uint8_t *qkeys, const ui
 {
     const hipError_t e = hipMemsetAsync(a.result, 0, 3 * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lzf_kidx_lookup_kernel, dim3(ki_grid(nq)), dim3(KI_BLOCK), 0, s, a, qkeys, q_off, q_len, nq, idx);
+    hipLaunchKernelGGL(lzf_kidx_lookup_kernel, dim3(sd_sweep_grid(nq)), dim3(SD_BLOCK), 0, s, a, qkeys, q_off, q_len, nq, idx);
     return hipGetLastError();
 }

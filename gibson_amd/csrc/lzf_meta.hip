@@ -29,7 +29,7 @@
  *   3. write (nothing unless LZF_MGET_OK): one lane per entry, its rank and
  *      offset from the tile's sums and a scan over the workgroup, then the
  *      pair.
- * Thread t of a tile takes entries t * MT_PER .. + MT_PER, so the scan over
+ * Thread t of a tile takes entries t * SD_PER .. + SD_PER, so the scan over
  * the threads is the scan over the list and the ranks are in list order.
  *
  * Counts by wave ballot, one atomic add per wave and counter.  The kernels are
@@ -38,80 +38,46 @@
  */
 #include <string.h>
 
-#include "lzf_dev.h"
+#include "lzf_store_dev.h"
 #include "../../include/lzf_gpu.h"
-
-#define MT_BLOCK 256u
-#define MT_PER   4u
-#define MT_TILE  (MT_BLOCK * MT_PER)      /* entries per keys tile */
-#define MT_WAVES (MT_BLOCK / 64u)
-#define MT_GRID  2048u                    /* grid-stride kernels: 256 CUs x 8 workgroups */
-
-static inline uint32_t mt_tiles(uint32_t n)
-{
-    return (uint32_t)(((uint64_t)n + MT_TILE - 1u) / MT_TILE);
-}
-
-static inline uint32_t mt_sweep_grid(uint64_t n)
-{
-    const uint64_t g = (n + MT_BLOCK - 1u) / MT_BLOCK;
-    return (uint32_t)(g < MT_GRID ? g : MT_GRID);
-}
 
 namespace {
 
 /* state words of the keys work area */
 enum { MT_FOUND = 0, MT_PAYLOAD = 1, MT_STATUS = 2 };
 
-__device__ inline uint32_t mt_count(bool x)
-{
-    return (uint32_t)__popcll(__ballot(x));
-}
-
-__device__ inline uint64_t mt_wave_sum(uint64_t x)
-{
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, d, 64);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), d, 64);
-        x += ((uint64_t)hi << 32) | lo;
-    }
-    return x;
-}
-
 /* ---- gc ------------------------------------------------------------------------ */
 
-/* src/server.c:318-326: eta = now - last_access, in two's complement as the
- * reference's time_t arithmetic wraps; freed iff eta && eta >= gc_ratio.
+/* src/server.c:318-326: eta = now - last_access (mg_age); freed iff eta &&
+ * eta >= gc_ratio.
  * Locks and TTLs are not consulted, as there.  result[0]: items freed, [1]:
  * their stored bytes, [2]: 1, the sweep ran */
-__global__ __launch_bounds__(MT_BLOCK) void lzf_store_gc_kernel(const int64_t *__restrict__ last_access, int64_t now,
-                                                                int64_t gc_ratio, uint8_t *enc,
-                                                                const uint32_t *__restrict__ val_size, uint32_t count,
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_gc_kernel(LzfItems it, int64_t gc_ratio,
+                                                                const uint32_t *__restrict__ val_size,
                                                                 const uint64_t *gate, uint64_t max_bytes,
                                                                 uint64_t *result)
 {
+    const int64_t *__restrict__ last_access = it.last_access;
     if (gate && *gate <= max_bytes) return;               /* src/server.c:403; the same for every lane */
     if (blockIdx.x == 0u && threadIdx.x == 0u) result[2] = 1ull;
-    const uint64_t step = (uint64_t)gridDim.x * MT_BLOCK;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint32_t freed = 0u;
     uint64_t bytes = 0ull;
-    for (uint64_t b = (uint64_t)blockIdx.x * MT_BLOCK; b < count; b += step) {
+    for (uint64_t b = (uint64_t)blockIdx.x * SD_BLOCK; b < it.count; b += step) {
         const uint64_t i = b + threadIdx.x;
         bool hit = false;
-        if (i < count && enc[i] != (uint8_t)LZF_ENC_NULL) {
-            const int64_t eta = (int64_t)((uint64_t)now - (uint64_t)last_access[i]);
+        if (i < it.count && it.enc[i] != (uint8_t)LZF_ENC_NULL) {
+            const int64_t eta = mg_age(it.now, last_access[i]);
             hit = eta != 0 && eta >= gc_ratio;
             if (hit) {
-                enc[i] = (uint8_t)LZF_ENC_NULL;           /* GB_DEL_ITEM */
+                it.enc[i] = (uint8_t)LZF_ENC_NULL;        /* GB_DEL_ITEM */
                 bytes += val_size[i];
             }
         }
-        freed += mt_count(hit);
+        freed += sd_count(hit);
     }
-    bytes = mt_wave_sum(bytes);
-    if ((threadIdx.x & 63u) != 0u) return;
-    if (freed) atomicAdd((unsigned long long *)result, (unsigned long long)freed);
-    if (bytes) atomicAdd((unsigned long long *)result + 1, (unsigned long long)bytes);
+    sd_leader_add(result, freed);
+    sd_leader_add(result + 1, sd_wave_sum(bytes));
 }
 
 /* ---- meta ---------------------------------------------------------------------- */
@@ -119,48 +85,47 @@ __global__ __launch_bounds__(MT_BLOCK) void lzf_store_gc_kernel(const int64_t *_
 /* gbQueryMetaHandler (src/query.c:1317-1335) over the list: the validity with
  * remove = 1, no lock test; the value, then last_access = now (:1330), so
  * ACCESS reports the time before this call.  result[0]: found, [1]: expired */
-__global__ __launch_bounds__(MT_BLOCK) void lzf_store_meta_kernel(LzfMetaArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_meta_kernel(LzfMetaArgs a)
 {
-    const uint64_t step = (uint64_t)gridDim.x * MT_BLOCK;
+    const LzfItems &it = a.it;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint32_t found = 0u, expired = 0u;
-    for (uint64_t b = (uint64_t)blockIdx.x * MT_BLOCK; b < a.n; b += step) {
+    for (uint64_t b = (uint64_t)blockIdx.x * SD_BLOCK; b < a.n; b += step) {
         const uint64_t k = b + threadIdx.x;
-        uint32_t st = 0xFFu;
+        uint32_t st = SD_NONE;
         if (k < a.n) {
             const uint32_t i = a.idx[k];
-            const int v = mg_validity(i, a.count, a.enc, a.item_time, a.item_ttl, a.now);
+            const int v = mg_validity(i, it);
             int64_t val = 0;
             if (v == MG_DEAD) {
                 st = LZF_ENT_DEAD;
             } else if (v == MG_EXPIRED) {
                 st = LZF_ENT_EXPIRED;
-                a.enc[i] = (uint8_t)LZF_ENC_NULL;
+                it.enc[i] = (uint8_t)LZF_ENC_NULL;
             } else {
                 st = LZF_ENT_DONE;
-                const int32_t ttl = a.item_ttl[i];
+                const int32_t ttl = it.item_ttl[i];
                 switch (a.field) {                        /* gbGetItemMeta, :1263-1297 */
                 case LZF_META_SIZE: val = (int64_t)a.val_size[i]; break;
-                case LZF_META_ENCODING: val = (int64_t)a.enc[i]; break;
-                case LZF_META_ACCESS: val = a.last_access[i]; break;
-                case LZF_META_CREATED: val = a.item_time[i]; break;
+                case LZF_META_ENCODING: val = (int64_t)it.enc[i]; break;
+                case LZF_META_ACCESS: val = it.last_access[i]; break;
+                case LZF_META_CREATED: val = it.item_time[i]; break;
                 case LZF_META_TTL: val = (int64_t)ttl; break;
                 case LZF_META_LEFT:                       /* :1290, the time arithmetic modulo 2^64 */
-                    val = ttl <= 0 ? -1
-                                   : (int64_t)((uint64_t)(int64_t)ttl - ((uint64_t)a.now - (uint64_t)a.item_time[i]));
+                    val = ttl <= 0 ? -1 : (int64_t)((uint64_t)(int64_t)ttl - (uint64_t)mg_age(it.now, it.item_time[i]));
                     break;
-                default: val = a.item_lock ? a.item_lock[i] : 0; break;
+                default: val = it.item_lock ? it.item_lock[i] : 0; break;
                 }
-                if (a.last_access) a.last_access[i] = a.now;
+                if (it.last_access) it.last_access[i] = it.now;
             }
             a.entry_value[k] = val;
             if (a.entry_status) a.entry_status[k] = (uint8_t)st;
         }
-        found += mt_count(st == LZF_ENT_DONE);
-        expired += mt_count(st == LZF_ENT_EXPIRED);
+        found += sd_count(st == LZF_ENT_DONE);
+        expired += sd_count(st == LZF_ENT_EXPIRED);
     }
-    if ((threadIdx.x & 63u) != 0u) return;
-    if (found) atomicAdd((unsigned long long *)a.result, (unsigned long long)found);
-    if (expired) atomicAdd((unsigned long long *)a.result + 1, (unsigned long long)expired);
+    sd_leader_add(a.result, found);
+    sd_leader_add(a.result + 1, expired);
 }
 
 /* ---- keys ---------------------------------------------------------------------- */
@@ -191,18 +156,13 @@ __device__ inline uint64_t mt_digits_below(uint64_t r)
     return sum;
 }
 
-__device__ inline void mt_put32(uint8_t *p, uint32_t x)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_keys_reduce_kernel(LzfKeysArgs a)
 {
-    p[0] = (uint8_t)x; p[1] = (uint8_t)(x >> 8); p[2] = (uint8_t)(x >> 16); p[3] = (uint8_t)(x >> 24);
-}
-
-__global__ __launch_bounds__(MT_BLOCK) void lzf_keys_reduce_kernel(LzfKeysArgs a)
-{
-    __shared__ uint64_t sw[MT_WAVES];
-    const uint64_t first = (uint64_t)blockIdx.x * MT_TILE + threadIdx.x * MT_PER;
+    __shared__ uint64_t sw[SD_WAVES];
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
     uint64_t cnt = 0ull, bytes = 0ull;
 #pragma unroll
-    for (uint32_t j = 0; j < MT_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         if (first + j >= a.n) continue;
         const uint32_t i = a.idx[first + j];
         if (!mt_takes_part(a, i)) continue;
@@ -210,8 +170,8 @@ __global__ __launch_bounds__(MT_BLOCK) void lzf_keys_reduce_kernel(LzfKeysArgs a
         bytes += a.key_len[i];
     }
     uint64_t tn, tb;
-    (void)dv_block_excl<MT_WAVES>(cnt, sw, &tn);
-    (void)dv_block_excl<MT_WAVES>(bytes, sw, &tb);
+    (void)dv_block_excl<SD_WAVES>(cnt, sw, &tn);
+    (void)dv_block_excl<SD_WAVES>(bytes, sw, &tb);
     if (threadIdx.x == 0u) {
         a.w_tile_n[blockIdx.x] = tn;
         a.w_tile_b[blockIdx.x] = tb;
@@ -220,11 +180,11 @@ __global__ __launch_bounds__(MT_BLOCK) void lzf_keys_reduce_kernel(LzfKeysArgs a
 
 /* one workgroup: the exclusive scans of the tile sums in place, and the call's
  * decision */
-__global__ __launch_bounds__(MT_BLOCK) void lzf_keys_scan_kernel(LzfKeysArgs a, uint32_t ntile)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_keys_scan_kernel(LzfKeysArgs a, uint32_t ntile)
 {
-    __shared__ uint64_t sw[MT_WAVES];
-    const uint64_t run_n = dv_carry_scan<MT_WAVES>(a.w_tile_n, ntile, sw);
-    const uint64_t run_b = dv_carry_scan<MT_WAVES>(a.w_tile_b, ntile, sw);
+    __shared__ uint64_t sw[SD_WAVES];
+    const uint64_t run_n = dv_carry_scan<SD_WAVES>(a.w_tile_n, ntile, sw);
+    const uint64_t run_b = dv_carry_scan<SD_WAVES>(a.w_tile_b, ntile, sw);
     if (threadIdx.x != 0u) return;
     /* u32 element count, then per pair [u32][digits][u8][u32][key]: below 2^65
      * only in theory -- found < 2^32 and the key bytes < 2^64 / 2 in any store */
@@ -237,27 +197,23 @@ __global__ __launch_bounds__(MT_BLOCK) void lzf_keys_scan_kernel(LzfKeysArgs a, 
     a.w_state[MT_STATUS] = st;
     a.result[0] = run_n;
     a.result[1] = st;
-    const uint64_t hdr = a.reply_header ? 7u : 0u;       /* [i16 code][u8 enc][u32 size] */
+    const uint64_t hdr = a.reply_header ? SD_HDR : 0u;
     *a.frame_len = st == (uint64_t)LZF_MGET_OK ? payload + hdr : 0ull;
     if (st != (uint64_t)LZF_MGET_OK) return;
     uint8_t *f = a.frame;
-    if (a.reply_header) {
-        f[0] = (uint8_t)LZF_REPL_KVAL; f[1] = (uint8_t)(LZF_REPL_KVAL >> 8);   /* src/net.c:1185 */
-        f[2] = LZF_ENC_PLAIN;                                                 /* src/net.c:1339 */
-        mt_put32(f + 3, (uint32_t)payload);
-    }
-    mt_put32(f + hdr, (uint32_t)run_n);                                       /* src/net.c:1282 */
+    if (a.reply_header) sd_put_header(f, LZF_REPL_KVAL, (uint8_t)LZF_ENC_PLAIN, (uint32_t)payload);   /* src/net.c:1339 */
+    sd_put32(f + hdr, (uint32_t)run_n);                                       /* src/net.c:1282 */
 }
 
-__global__ __launch_bounds__(MT_BLOCK) void lzf_keys_write_kernel(LzfKeysArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_keys_write_kernel(LzfKeysArgs a)
 {
-    __shared__ uint64_t sw[MT_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     if (a.w_state[MT_STATUS] != (uint64_t)LZF_MGET_OK) return;   /* the same for every lane */
-    const uint64_t first = (uint64_t)blockIdx.x * MT_TILE + threadIdx.x * MT_PER;
-    uint32_t item[MT_PER], kl[MT_PER];
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
+    uint32_t item[SD_PER], kl[SD_PER];
     uint64_t cnt = 0ull, bytes = 0ull;
 #pragma unroll
-    for (uint32_t j = 0; j < MT_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         kl[j] = 0u;                                       /* 0: the entry does not take part */
         item[j] = 0u;
         if (first + j >= a.n) continue;
@@ -269,21 +225,21 @@ __global__ __launch_bounds__(MT_BLOCK) void lzf_keys_write_kernel(LzfKeysArgs a)
         bytes += kl[j];
     }
     uint64_t tn, tb;
-    uint64_t rank = a.w_tile_n[blockIdx.x] + dv_block_excl<MT_WAVES>(cnt, sw, &tn);
-    uint64_t kb = a.w_tile_b[blockIdx.x] + dv_block_excl<MT_WAVES>(bytes, sw, &tb);
+    uint64_t rank = a.w_tile_n[blockIdx.x] + dv_block_excl<SD_WAVES>(cnt, sw, &tn);
+    uint64_t kb = a.w_tile_b[blockIdx.x] + dv_block_excl<SD_WAVES>(bytes, sw, &tb);
     if (!cnt) return;
     /* every byte written lies below hdr + payload <= hdr + max_response */
-    uint8_t *f = a.frame + (a.reply_header ? 7u : 0u) + 4u + 9ull * rank + mt_digits_below(rank) + kb;
+    uint8_t *f = a.frame + (a.reply_header ? SD_HDR : 0u) + 4u + 9ull * rank + mt_digits_below(rank) + kb;
 #pragma unroll
-    for (uint32_t j = 0; j < MT_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         if (!kl[j]) continue;
         const uint32_t nd = mt_digits(rank);
-        mt_put32(f, nd);                                  /* the KVAL key: sprintf "%lu" of the rank (:1364) */
+        sd_put32(f, nd);                                  /* the KVAL key: sprintf "%lu" of the rank (:1364) */
         uint64_t r = rank;
         for (uint32_t d = nd; d-- > 0u; r /= 10ull) f[4u + d] = (uint8_t)('0' + (uint32_t)(r % 10ull));
         f += 4u + nd;
         f[0] = (uint8_t)LZF_ENC_PLAIN;                    /* gbCreateVolatileItem(..., GB_ENC_PLAIN), :1367 */
-        mt_put32(f + 1, kl[j]);
+        sd_put32(f + 1, kl[j]);
         const uint8_t *key = a.keys + a.key_off[item[j]];
         for (uint32_t c = 0; c < kl[j]; c++) f[5u + c] = key[c];
         f += 5ull + kl[j];
@@ -308,14 +264,13 @@ int lzf_meta_field(const uint8_t *m, uint32_t mlen)
     return -1;
 }
 
-hipError_t lzf_launch_store_gc(const int64_t *last_access, int64_t now, int64_t gc_ratio, uint8_t *enc,
-                               const uint32_t *val_size, uint32_t count, const uint64_t *gate, uint64_t max_bytes,
-                               uint64_t *result, hipStream_t s)
+hipError_t lzf_launch_store_gc(const LzfItems &it, int64_t gc_ratio, const uint32_t *val_size, const uint64_t *gate,
+                               uint64_t max_bytes, uint64_t *result, hipStream_t s)
 {
     const hipError_t e = hipMemsetAsync(result, 0, 3 * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lzf_store_gc_kernel, dim3(mt_sweep_grid(count)), dim3(MT_BLOCK), 0, s, last_access, now,
-                       gc_ratio, enc, val_size, count, gate, max_bytes, result);
+    hipLaunchKernelGGL(lzf_store_gc_kernel, dim3(sd_sweep_grid(it.count)), dim3(SD_BLOCK), 0, s, it, gc_ratio, val_size,
+                       gate, max_bytes, result);
     return hipGetLastError();
 }
 
@@ -323,32 +278,17 @@ hipError_t lzf_launch_store_meta(const LzfMetaArgs &a, hipStream_t s)
 {
     const hipError_t e = hipMemsetAsync(a.result, 0, 2 * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lzf_store_meta_kernel, dim3(mt_sweep_grid(a.n)), dim3(MT_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_store_meta_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
     return hipGetLastError();
-}
-
-uint64_t lzf_keys_work_bytes(uint32_t n)
-{
-    /* state (8 x u64) | two tile sums (u64 per tile); room to align the caller's pointer */
-    return 64u + (uint64_t)mt_tiles(n) * 16u + 16u;
-}
-
-void lzf_keys_carve(LzfKeysArgs &a, void *work)
-{
-    uint8_t *w = (uint8_t *)(((uintptr_t)work + 7u) & ~(uintptr_t)7u);
-    const size_t nt = mt_tiles(a.n);
-    a.w_state = (uint64_t *)w;            w += 64;
-    a.w_tile_n = (uint64_t *)w;           w += nt * 8;
-    a.w_tile_b = (uint64_t *)w;
 }
 
 hipError_t lzf_launch_store_keys(LzfKeysArgs &a, hipStream_t s)
 {
     const hipError_t e = hipMemsetAsync(a.result, 0, 2 * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    const uint32_t nt = mt_tiles(a.n);
-    hipLaunchKernelGGL(lzf_keys_reduce_kernel, dim3(nt), dim3(MT_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(lzf_keys_scan_kernel, dim3(1), dim3(MT_BLOCK), 0, s, a, nt);
-    hipLaunchKernelGGL(lzf_keys_write_kernel, dim3(nt), dim3(MT_BLOCK), 0, s, a);
+    const uint32_t nt = sd_tiles(a.n);
+    hipLaunchKernelGGL(lzf_keys_reduce_kernel, dim3(nt), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_keys_scan_kernel, dim3(1), dim3(SD_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_keys_write_kernel, dim3(nt), dim3(SD_BLOCK), 0, s, a);
     return hipGetLastError();
 }

@@ -38,7 +38,7 @@
  * once -- and stores it with one aligned 16-byte store.  The first and the
  * last granule of the range may be partial and are stored byte-exactly
  * (dv_st_exact).  The grid is sized by bytes, from the host's bound vlen * n,
- * one granule per lane up to OP_GRID workgroups and grid-stride past that,
+ * one granule per lane up to SD_GRID workgroups and grid-stride past that,
  * four granules in flight per lane; workgroups past the real range (S < vlen,
  * done < n) leave at once.  b mod S is one 64-bit division per lane, then an
  * add and a compare per granule.  src is at most 64 MiB read by every
@@ -47,52 +47,22 @@
  * The kernels are helpers of this translation unit, not part of the library's
  * routed kernel set: they have internal linkage (anonymous namespace).
  */
-#include "lzf_dev.h"
+#include "lzf_store_dev.h"
 #include "gb_policy.h"
 #include "../../include/lzf_gpu.h"
 
-#define MS_BLOCK 256u
-#define MS_PER   4u
-#define MS_TILE  (MS_BLOCK * MS_PER)      /* entries per tile */
-#define MS_WAVES (MS_BLOCK / 64u)
-#define MS_GRID  2048u                    /* 256 CUs x 8 workgroups */
-#define MS_NONE  0xFFu                    /* no entry: a lane past the list's end */
-#define MS_UNROLL 4u                      /* granules in flight per lane */
-
-static inline uint32_t ms_tiles(uint32_t n)
-{
-    return (uint32_t)(((uint64_t)n + MS_TILE - 1u) / MS_TILE);
-}
-
-/* the compress slot: gb_needcompr(vlen) bytes at most, rounded up */
-static inline uint64_t ms_slot_bytes(uint32_t vlen)
-{
-    return ((uint64_t)vlen + vlen / 16u + 8u + 15u) & ~15ull;
-}
+/* the replicate kernel's own: granules in flight per lane.  The rest of the
+ * geometry is the toolkit's (lzf_store_dev.h) */
+#define MS_UNROLL 4u
 
 namespace {
 
 /* state words of the work area */
 enum { MS_BASE = 0, MS_FULL = 1, MS_SIZE = 2, MS_ENC = 3, MS_DONE = 4 };
 
-__device__ inline uint32_t ms_count(bool x)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_mset_classify_kernel(LzfMsetArgs a)
 {
-    return (uint32_t)__popcll(__ballot(x));
-}
-
-/* gbMultiSetCallback (src/query.c:490-502): dead, then the lock -- on an
- * expired item too (:493 comes before :496) -- then the validity.  Reads only */
-__device__ inline uint32_t ms_class(const LzfMsetArgs &a, uint32_t i)
-{
-    const int v = mg_validity(i, a.count, a.enc, a.item_time, a.item_ttl, a.now);
-    if (v == MG_DEAD) return LZF_ENT_DEAD;
-    if (mg_locked(i, a.item_time, a.item_lock, a.now)) return LZF_ENT_LOCKED;
-    return v == MG_EXPIRED ? LZF_ENT_EXPIRED : LZF_ENT_DONE;
-}
-
-__global__ __launch_bounds__(MS_BLOCK) void lzf_mset_classify_kernel(LzfMsetArgs a)
-{
-    __shared__ uint64_t sw[MS_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     if (blockIdx.x == 0u && threadIdx.x == 0u) {
         /* the batch of one value: a candidate iff vlen > compression
          * (src/query.c:389, strict), else length 0, which yields out_len 0 */
@@ -102,27 +72,29 @@ __global__ __launch_bounds__(MS_BLOCK) void lzf_mset_classify_kernel(LzfMsetArgs
         a.c_len[1] = gb_needcompr(a.vlen);                /* out_cap */
         a.c_len[2] = 0u;                                  /* out_len */
     }
-    const uint64_t first = (uint64_t)blockIdx.x * MS_TILE + threadIdx.x * MS_PER;
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
     uint64_t done = 0ull;
 #pragma unroll
-    for (uint32_t j = 0; j < MS_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         const uint64_t k = first + j;
         if (k >= a.n) continue;
-        const uint32_t cls = ms_class(a, a.idx[k]);
+        /* gbMultiSetCallback (src/query.c:490-502): dead, then the lock -- on an
+         * expired item too (:493 comes before :496) -- then the validity */
+        const uint32_t cls = sd_entry_class(a.idx[k], a.it, false);
         a.w_cls[k] = (uint8_t)cls;
         done += cls == LZF_ENT_DONE;
     }
     uint64_t tot;
-    (void)dv_block_excl<MS_WAVES>(done, sw, &tot);
+    (void)dv_block_excl<SD_WAVES>(done, sw, &tot);
     if (threadIdx.x == 0u) a.w_tile[blockIdx.x] = tot;
 }
 
 /* one workgroup: the exclusive scan of the tile counts in place, the stored
  * form, and the call's decision */
-__global__ __launch_bounds__(MS_BLOCK) void lzf_mset_scan_kernel(LzfMsetArgs a, uint32_t ntile)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_mset_scan_kernel(LzfMsetArgs a, uint32_t ntile)
 {
-    __shared__ uint64_t sw[MS_WAVES];
-    const uint64_t run = dv_carry_scan<MS_WAVES>(a.w_tile, ntile, sw);
+    __shared__ uint64_t sw[SD_WAVES];
+    const uint64_t run = dv_carry_scan<SD_WAVES>(a.w_tile, ntile, sw);
     if (threadIdx.x != 0u) return;
     /* a stream or the plain bytes, as the store decision of lzf_store.hip */
     const uint32_t got = a.c_len[2];
@@ -143,53 +115,51 @@ __global__ __launch_bounds__(MS_BLOCK) void lzf_mset_scan_kernel(LzfMsetArgs a, 
     a.result[4] = enc;
 }
 
-__global__ __launch_bounds__(MS_BLOCK) void lzf_mset_apply_kernel(LzfMsetArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_mset_apply_kernel(LzfMsetArgs a)
 {
-    __shared__ uint64_t sw[MS_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     if (a.w_state[MS_FULL]) return;                       /* refused: the same for every lane */
-    const uint64_t first = (uint64_t)blockIdx.x * MS_TILE + threadIdx.x * MS_PER;
-    uint32_t cls[MS_PER];
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
+    uint32_t cls[SD_PER];
     uint64_t mine = 0ull;
 #pragma unroll
-    for (uint32_t j = 0; j < MS_PER; j++) {
-        cls[j] = first + j < a.n ? a.w_cls[first + j] : MS_NONE;
+    for (uint32_t j = 0; j < SD_PER; j++) {
+        cls[j] = first + j < a.n ? a.w_cls[first + j] : SD_NONE;
         mine += cls[j] == LZF_ENT_DONE;
     }
     uint64_t tot;
-    uint64_t rank = a.w_tile[blockIdx.x] + dv_block_excl<MS_WAVES>(mine, sw, &tot);
+    uint64_t rank = a.w_tile[blockIdx.x] + dv_block_excl<SD_WAVES>(mine, sw, &tot);
     const uint64_t base = a.w_state[MS_BASE], size = a.w_state[MS_SIZE];
     const uint8_t enc = (uint8_t)a.w_state[MS_ENC];
     uint32_t done = 0u, expired = 0u, locked = 0u;
 #pragma unroll
-    for (uint32_t j = 0; j < MS_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         const uint64_t k = first + j;
         const uint32_t c = cls[j];
-        if (c != MS_NONE) {
+        if (c != SD_NONE) {
             const uint32_t i = a.idx[k];
             if (c == LZF_ENT_EXPIRED) {
-                a.enc[i] = (uint8_t)LZF_ENC_NULL;
+                a.it.enc[i] = (uint8_t)LZF_ENC_NULL;
             } else if (c == LZF_ENT_DONE) {
                 /* gbCreateItem (src/query.c:113-146) with ttl -1 (:417) */
                 a.val_off[i] = base + size * rank++;      /* its end <= store_cap: the scan's decision */
                 a.val_size[i] = (uint32_t)size;
-                a.enc[i] = enc;
+                a.it.enc[i] = enc;
                 a.val_len[i] = a.vlen;
-                a.item_time[i] = a.now;
-                a.item_ttl[i] = -1;
-                if (a.item_lock) a.item_lock[i] = 0;
-                if (a.last_access) a.last_access[i] = a.now;
+                a.it.item_time[i] = a.it.now;
+                a.it.item_ttl[i] = -1;
+                if (a.it.item_lock) a.it.item_lock[i] = 0;
+                if (a.it.last_access) a.it.last_access[i] = a.it.now;
             }
             if (a.entry_status) a.entry_status[k] = (uint8_t)c;
         }
-        done += ms_count(c == LZF_ENT_DONE);
-        expired += ms_count(c == LZF_ENT_EXPIRED);
-        locked += ms_count(c == LZF_ENT_LOCKED);
+        done += sd_count(c == LZF_ENT_DONE);
+        expired += sd_count(c == LZF_ENT_EXPIRED);
+        locked += sd_count(c == LZF_ENT_LOCKED);
     }
-    if ((threadIdx.x & 63u) != 0u) return;
-    unsigned long long *r = (unsigned long long *)a.result;
-    if (done) atomicAdd(r, (unsigned long long)done);
-    if (expired) atomicAdd(r + 1, (unsigned long long)expired);
-    if (locked) atomicAdd(r + 2, (unsigned long long)locked);
+    sd_leader_add(a.result, done);
+    sd_leader_add(a.result + 1, expired);
+    sd_leader_add(a.result + 2, locked);
 }
 
 /* v shifted up by sh (0 .. 15) bytes, zeros in */
@@ -229,7 +199,7 @@ __device__ inline uint4 ms_cyclic16(const uint8_t *__restrict__ src, uint32_t S,
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-__global__ __launch_bounds__(MS_BLOCK) void lzf_mset_replicate_kernel(LzfMsetArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_mset_replicate_kernel(LzfMsetArgs a)
 {
     if (a.w_state[MS_FULL]) return;
     const uint32_t S = (uint32_t)a.w_state[MS_SIZE];
@@ -242,8 +212,8 @@ __global__ __launch_bounds__(MS_BLOCK) void lzf_mset_replicate_kernel(LzfMsetArg
     const uint64_t a0 = d0 & ~15ull;
     const uint32_t head = (uint32_t)(d0 - a0);
     const uint64_t ngran = (d1 - a0 + 15u) / 16u;
-    const uint64_t stride = (uint64_t)gridDim.x * MS_BLOCK;
-    uint64_t j = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
+    const uint64_t stride = (uint64_t)gridDim.x * SD_BLOCK;
+    uint64_t j = (uint64_t)blockIdx.x * SD_BLOCK + threadIdx.x;
     if (j >= ngran) return;
     const uint4 pat = S < 16u ? dv_ld16_tail(src, S) : make_uint4(0u, 0u, 0u, 0u);
     uint8_t *__restrict__ const store = a.store;
@@ -282,43 +252,23 @@ __global__ __launch_bounds__(MS_BLOCK) void lzf_mset_replicate_kernel(LzfMsetArg
 
 }  // namespace
 
-uint64_t lzf_mset_work_bytes(uint32_t n, uint32_t vlen)
-{
-    /* state (8 x u64) | the compress batch's descriptors (2 x u64, 3 x u32, to
-     * 64) | tile counts (u64 per tile) | the classes (u8, rounded up) | the
-     * compress slot; room to align the caller's pointer.  Below 2^34 */
-    return 64u + 64u + (uint64_t)ms_tiles(n) * 8u + (((uint64_t)n + 15u) & ~15ull) + ms_slot_bytes(vlen) + 16u;
-}
-
-void lzf_mset_carve(LzfMsetArgs &a, void *work)
-{
-    uint8_t *w = (uint8_t *)(((uintptr_t)work + 15u) & ~(uintptr_t)15u);
-    a.w_state = (uint64_t *)w;            w += 64;
-    a.c_off = (uint64_t *)w;
-    a.c_len = (uint32_t *)(w + 16);       w += 64;
-    a.w_tile = (uint64_t *)w;             w += (size_t)ms_tiles(a.n) * 8;
-    a.w_cls = w;                          w += ((size_t)a.n + 15u) & ~(size_t)15u;
-    w = (uint8_t *)(((uintptr_t)w + 15u) & ~(uintptr_t)15u);
-    a.w_slot = w;
-}
-
 hipError_t lzf_launch_store_mset(LzfMsetArgs &a, hipStream_t s, hipError_t (*compress)(const LzfBatch &, hipStream_t))
 {
     hipError_t e = hipMemsetAsync(a.result, 0, 5 * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    const uint32_t nt = ms_tiles(a.n);
-    hipLaunchKernelGGL(lzf_mset_classify_kernel, dim3(nt), dim3(MS_BLOCK), 0, s, a);
+    const uint32_t nt = sd_tiles(a.n);
+    hipLaunchKernelGGL(lzf_mset_classify_kernel, dim3(nt), dim3(SD_BLOCK), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (a.vlen > a.compression) {
         LzfBatch b{a.value, a.c_off, a.c_len, a.w_slot, a.c_off + 1, a.c_len + 1, a.c_len + 2, nullptr, 1u, a.vlen};
         if ((e = compress(b, s)) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(lzf_mset_scan_kernel, dim3(1), dim3(MS_BLOCK), 0, s, a, nt);
-    hipLaunchKernelGGL(lzf_mset_apply_kernel, dim3(nt), dim3(MS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_mset_scan_kernel, dim3(1), dim3(SD_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_mset_apply_kernel, dim3(nt), dim3(SD_BLOCK), 0, s, a);
     /* the host's bound on the range: n copies of vlen bytes, and a partial granule at either end */
     const uint64_t gran = ((uint64_t)a.vlen * a.n + 15u) / 16u + 1u;
-    const uint64_t wg = (gran + MS_BLOCK - 1u) / MS_BLOCK;
-    hipLaunchKernelGGL(lzf_mset_replicate_kernel, dim3((uint32_t)(wg < MS_GRID ? wg : MS_GRID)), dim3(MS_BLOCK), 0, s,
+    const uint64_t wg = (gran + SD_BLOCK - 1u) / SD_BLOCK;
+    hipLaunchKernelGGL(lzf_mset_replicate_kernel, dim3((uint32_t)(wg < SD_GRID ? wg : SD_GRID)), dim3(SD_BLOCK), 0, s,
                        a);
     return hipGetLastError();
 }

@@ -5,7 +5,8 @@
  * key.  With lzf_mget.hip they are the reference's operator table: each is the
  * callback of a tr_search (src/query.c:778-800, 898-940, 1015-1036, 1097-1114)
  * applied to an index list, one lane per entry, under the validity rule
- * (mg_validity) and the lock rule (mg_locked) of lzf_dev.h.
+ * (mg_validity), the lock rule (mg_locked) and their order (sd_entry_class)
+ * of lzf_store_dev.h, whose geometry, counts and scans the kernels use.
  *
  * mlock / munlock / mdel: one grid-stride pass over the list, as count and
  * mttl are; the counts by wave ballot, one atomic add per wave and counter.
@@ -23,7 +24,7 @@
  *      converted ones from the classes alone, then what its class says --
  *      enc nulled, the number stored in place or at base + 8 * rank,
  *      last_access, entry_status, entry_value -- and the six counts.
- * Thread t of a tile takes entries t * OP_PER .. + OP_PER, so the scan over
+ * Thread t of a tile takes entries t * SD_PER .. + SD_PER, so the scan over
  * the threads is the scan over the list and the ranks are in list order.
  * Stored numbers sit at any alignment (the arena is dense): they are read and
  * written as 8 unaligned bytes, never by a 64-bit atomic.
@@ -33,20 +34,8 @@
  * The kernels are helpers of this translation unit, not part of the library's
  * routed kernel set: they have internal linkage (anonymous namespace).
  */
-#include "lzf_dev.h"
+#include "lzf_store_dev.h"
 #include "../../include/lzf_gpu.h"
-
-#define OP_BLOCK 256u
-#define OP_PER   4u
-#define OP_TILE  (OP_BLOCK * OP_PER)      /* entries per minc tile */
-#define OP_WAVES (OP_BLOCK / 64u)
-#define OP_GRID  2048u                    /* grid-stride kernels: 256 CUs x 8 workgroups */
-#define OP_NONE  0xFFu                    /* no entry: a lane past the list's end */
-
-static inline uint32_t op_tiles(uint32_t n)
-{
-    return (uint32_t)(((uint64_t)n + OP_TILE - 1u) / OP_TILE);
-}
 
 namespace {
 
@@ -55,11 +44,6 @@ enum { OP_MLOCK = 0, OP_MUNLOCK = 1, OP_MDEL = 2 };
 /* state words of the minc work area */
 enum { OP_BASE = 0, OP_FULL = 1 };
 
-__device__ inline uint32_t op_count(bool x)
-{
-    return (uint32_t)__popcll(__ballot(x));
-}
-
 /* ---- mlock, munlock, mdel ----------------------------------------------------- */
 
 /* gbMultiLockCallback (src/query.c:1015-1036), gbMultiUnlockCallback
@@ -67,48 +51,49 @@ __device__ inline uint32_t op_count(bool x)
  * a workgroup makes the same number of rounds.  result[0]: entries the
  * operator applied to, [1]: expired ones, [2] (not MUNLOCK): locked ones */
 template <int OP>
-__global__ __launch_bounds__(OP_BLOCK) void lzf_store_lock_kernel(LzfLockArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_lock_kernel(LzfLockArgs a)
 {
-    const uint64_t step = (uint64_t)gridDim.x * OP_BLOCK;
+    const LzfItems &it = a.it;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint32_t done = 0u, expired = 0u, locked = 0u;
-    for (uint64_t b = (uint64_t)blockIdx.x * OP_BLOCK; b < a.n; b += step) {
+    for (uint64_t b = (uint64_t)blockIdx.x * SD_BLOCK; b < a.n; b += step) {
         const uint64_t k = b + threadIdx.x;
-        uint32_t st = OP_NONE;
+        uint32_t st = SD_NONE;
         if (k < a.n) {
             const uint32_t i = a.idx[k];
-            const int v = mg_validity(i, a.count, a.enc, a.item_time, a.item_ttl, a.now);
-            if (v == MG_DEAD) {
-                st = LZF_ENT_DEAD;
-            } else if (OP == OP_MDEL) {
+            if (OP == OP_MDEL) {
                 /* the lock is tested first, on an expired item too (:789-792) */
-                if (mg_locked(i, a.item_time, a.item_lock, a.now)) st = LZF_ENT_LOCKED;
-                else st = v == MG_EXPIRED ? LZF_ENT_EXPIRED : LZF_ENT_DONE;
-                if (st != LZF_ENT_LOCKED) a.enc[i] = (uint8_t)LZF_ENC_NULL;
-            } else if (v == MG_EXPIRED) {
-                st = LZF_ENT_EXPIRED;
-                a.enc[i] = (uint8_t)LZF_ENC_NULL;
-            } else if (OP == OP_MUNLOCK) {
-                st = LZF_ENT_DONE;
-                a.item_lock[i] = 0;                       /* :1107-1108 */
-                if (a.last_access) a.last_access[i] = a.now;
-            } else if (mg_locked(i, a.item_time, a.item_lock, a.now)) {
-                st = LZF_ENT_LOCKED;
+                st = sd_entry_class(i, it, false);
+                if (st == LZF_ENT_DONE || st == LZF_ENT_EXPIRED) it.enc[i] = (uint8_t)LZF_ENC_NULL;
             } else {
-                st = LZF_ENT_DONE;
-                a.item_time[i] = a.now;                   /* :1028-1030: the TTL clock restarts */
-                if (a.last_access) a.last_access[i] = a.now;
-                a.item_lock[i] = a.lock_time;
+                const int v = mg_validity(i, it);
+                if (v == MG_DEAD) {
+                    st = LZF_ENT_DEAD;
+                } else if (v == MG_EXPIRED) {
+                    st = LZF_ENT_EXPIRED;
+                    it.enc[i] = (uint8_t)LZF_ENC_NULL;
+                } else if (OP == OP_MUNLOCK) {
+                    st = LZF_ENT_DONE;
+                    it.item_lock[i] = 0;                  /* :1107-1108 */
+                    if (it.last_access) it.last_access[i] = it.now;
+                } else if (mg_locked(i, it)) {
+                    st = LZF_ENT_LOCKED;
+                } else {
+                    st = LZF_ENT_DONE;
+                    it.item_time[i] = it.now;             /* :1028-1030: the TTL clock restarts */
+                    if (it.last_access) it.last_access[i] = it.now;
+                    it.item_lock[i] = a.lock_time;
+                }
             }
             if (a.entry_status) a.entry_status[k] = (uint8_t)st;
         }
-        done += op_count(st == LZF_ENT_DONE);
-        expired += op_count(st == LZF_ENT_EXPIRED);
-        if (OP != OP_MUNLOCK) locked += op_count(st == LZF_ENT_LOCKED);
+        done += sd_count(st == LZF_ENT_DONE);
+        expired += sd_count(st == LZF_ENT_EXPIRED);
+        if (OP != OP_MUNLOCK) locked += sd_count(st == LZF_ENT_LOCKED);
     }
-    if ((threadIdx.x & 63u) != 0u) return;
-    if (done) atomicAdd((unsigned long long *)a.result, (unsigned long long)done);
-    if (expired) atomicAdd((unsigned long long *)a.result + 1, (unsigned long long)expired);
-    if (OP != OP_MUNLOCK && locked) atomicAdd((unsigned long long *)a.result + 2, (unsigned long long)locked);
+    sd_leader_add(a.result, done);
+    sd_leader_add(a.result + 1, expired);
+    if (OP != OP_MUNLOCK) sd_leader_add(a.result + 2, locked);
 }
 
 /* ---- minc --------------------------------------------------------------------- */
@@ -136,16 +121,13 @@ __device__ inline void op_st_i64(uint8_t *p, int64_t x)
  * gbQueryIncDecHandler (:853-886).  Reads only */
 __device__ inline uint32_t op_minc_class(const LzfMincArgs &a, uint32_t i, int64_t *val)
 {
-    const int v = mg_validity(i, a.count, a.enc, a.item_time, a.item_ttl, a.now);
-    if (v == MG_DEAD) return LZF_ENT_DEAD;
-    if (a.single) {
-        if (v == MG_EXPIRED) return LZF_ENT_EXPIRED;                                  /* :853 */
-        if (mg_locked(i, a.item_time, a.item_lock, a.now)) return LZF_ENT_LOCKED;     /* :858 */
-    } else {
-        if (mg_locked(i, a.item_time, a.item_lock, a.now)) return LZF_ENT_LOCKED;     /* :910 */
-        if (v == MG_EXPIRED) return LZF_ENT_EXPIRED;                                  /* :913 */
-    }
-    const uint8_t e = a.enc[i];
+    /* the encoding is read once, here, ahead of the class rule, whose own range test and read the compiler
+     * then folds into these: read after the rule it is one more scattered load per entry, a tenth of the pass */
+    if (i >= a.it.count) return LZF_ENT_DEAD;
+    const uint8_t e = a.it.enc[i];
+    /* single: the expiry (:853), then the lock (:858); else the lock (:910), then the expiry (:913) */
+    const uint32_t c = sd_entry_class(i, a.it, a.single != 0);
+    if (c != LZF_ENT_DONE) return c;
     const uint64_t off = a.val_off[i];
     const uint32_t size = a.val_size[i];
     if (e == (uint8_t)LZF_ENC_NUMBER) {
@@ -166,13 +148,13 @@ __device__ inline uint32_t op_minc_class(const LzfMincArgs &a, uint32_t i, int64
     return a.single ? LZF_ENT_NAN : LZF_ENT_UNCHANGED;
 }
 
-__global__ __launch_bounds__(OP_BLOCK) void lzf_minc_classify_kernel(LzfMincArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_minc_classify_kernel(LzfMincArgs a)
 {
-    __shared__ uint64_t sw[OP_WAVES];
-    const uint64_t first = (uint64_t)blockIdx.x * OP_TILE + threadIdx.x * OP_PER;
+    __shared__ uint64_t sw[SD_WAVES];
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
     uint64_t conv = 0ull;
 #pragma unroll
-    for (uint32_t j = 0; j < OP_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         const uint64_t k = first + j;
         if (k >= a.n) continue;
         int64_t val = 0;
@@ -182,35 +164,16 @@ __global__ __launch_bounds__(OP_BLOCK) void lzf_minc_classify_kernel(LzfMincArgs
         conv += cls == LZF_ENT_CONVERTED;
     }
     uint64_t tot;
-    (void)dv_block_excl<OP_WAVES>(conv, sw, &tot);
+    (void)dv_block_excl<SD_WAVES>(conv, sw, &tot);
     if (threadIdx.x == 0u) a.w_tile[blockIdx.x] = tot;
 }
 
-/* one workgroup: the exclusive scan of the tile counts in place, in pieces of
- * OP_BLOCK * OP_CARRY_PER with a running carry (as the select's carry kernel),
- * and the call's decision */
-#define OP_CARRY_PER 8u
-__global__ __launch_bounds__(OP_BLOCK) void lzf_minc_scan_kernel(LzfMincArgs a, uint32_t ntile)
+/* one workgroup: the exclusive scan of the tile counts in place, and the call's
+ * decision */
+__global__ __launch_bounds__(SD_BLOCK) void lzf_minc_scan_kernel(LzfMincArgs a, uint32_t ntile)
 {
-    __shared__ uint64_t sw[OP_WAVES];
-    uint64_t run = 0ull;
-    for (uint64_t c = 0; c < ntile; c += OP_BLOCK * OP_CARRY_PER) {
-        const uint64_t first = c + threadIdx.x * OP_CARRY_PER;
-        uint64_t v[OP_CARRY_PER], s = 0ull;
-#pragma unroll
-        for (uint32_t j = 0; j < OP_CARRY_PER; j++) {
-            v[j] = first + j < ntile ? a.w_tile[first + j] : 0ull;
-            s += v[j];
-        }
-        uint64_t tot;
-        uint64_t o = run + dv_block_excl<OP_WAVES>(s, sw, &tot);
-#pragma unroll
-        for (uint32_t j = 0; j < OP_CARRY_PER; j++) {
-            if (first + j < ntile) a.w_tile[first + j] = o;
-            o += v[j];
-        }
-        run += tot;
-    }
+    __shared__ uint64_t sw[SD_WAVES];
+    const uint64_t run = dv_carry_scan<SD_WAVES>(a.w_tile, ntile, sw);
     if (threadIdx.x != 0u) return;
     /* run <= n < 2^32: 8 * run cannot wrap, the sum can */
     const uint64_t base = *a.store_used, end = base + 8ull * run;
@@ -221,33 +184,33 @@ __global__ __launch_bounds__(OP_BLOCK) void lzf_minc_scan_kernel(LzfMincArgs a, 
     if (!full) *a.store_used = end;
 }
 
-__global__ __launch_bounds__(OP_BLOCK) void lzf_minc_apply_kernel(LzfMincArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_minc_apply_kernel(LzfMincArgs a)
 {
-    __shared__ uint64_t sw[OP_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     if (a.w_state[OP_FULL]) return;                       /* refused: the same for every lane */
-    const uint64_t first = (uint64_t)blockIdx.x * OP_TILE + threadIdx.x * OP_PER;
-    uint32_t cls[OP_PER];
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
+    uint32_t cls[SD_PER];
     uint64_t conv = 0ull;
 #pragma unroll
-    for (uint32_t j = 0; j < OP_PER; j++) {
-        cls[j] = first + j < a.n ? a.w_cls[first + j] : OP_NONE;
+    for (uint32_t j = 0; j < SD_PER; j++) {
+        cls[j] = first + j < a.n ? a.w_cls[first + j] : SD_NONE;
         conv += cls[j] == LZF_ENT_CONVERTED;
     }
     uint64_t tot;
-    uint64_t rank = a.w_tile[blockIdx.x] + dv_block_excl<OP_WAVES>(conv, sw, &tot);
+    uint64_t rank = a.w_tile[blockIdx.x] + dv_block_excl<SD_WAVES>(conv, sw, &tot);
     const uint64_t base = a.w_state[OP_BASE];
     uint32_t done = 0u, expired = 0u, locked = 0u, nan = 0u, converted = 0u, unchanged = 0u;
 #pragma unroll
-    for (uint32_t j = 0; j < OP_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         const uint64_t k = first + j;
         const uint32_t c = cls[j];
-        if (c != OP_NONE) {
+        if (c != SD_NONE) {
             const uint32_t i = a.idx[k];
             int64_t val = 0;
-            if (c == LZF_ENT_EXPIRED) a.enc[i] = (uint8_t)LZF_ENC_NULL;
+            if (c == LZF_ENT_EXPIRED) a.it.enc[i] = (uint8_t)LZF_ENC_NULL;
             /* every valid entry, a NAN one too: :861, :917 come before the value test */
             if (c == LZF_ENT_DONE || c == LZF_ENT_CONVERTED || c == LZF_ENT_NAN || c == LZF_ENT_UNCHANGED)
-                if (a.last_access) a.last_access[i] = a.now;
+                if (a.it.last_access) a.it.last_access[i] = a.it.now;
             if (c == LZF_ENT_DONE) {
                 val = a.w_val[k];
                 op_st_i64(a.store + a.val_off[i], val);   /* its range was checked by the classify pass */
@@ -257,27 +220,24 @@ __global__ __launch_bounds__(OP_BLOCK) void lzf_minc_apply_kernel(LzfMincArgs a)
                 op_st_i64(a.store + slot, val);
                 a.val_off[i] = slot;
                 a.val_size[i] = 8u;
-                a.enc[i] = (uint8_t)LZF_ENC_NUMBER;
+                a.it.enc[i] = (uint8_t)LZF_ENC_NUMBER;
             }
             if (a.entry_status) a.entry_status[k] = (uint8_t)c;
             if (a.entry_value) a.entry_value[k] = val;
         }
-        done += op_count(c == LZF_ENT_DONE);
-        expired += op_count(c == LZF_ENT_EXPIRED);
-        locked += op_count(c == LZF_ENT_LOCKED);
-        nan += op_count(c == LZF_ENT_NAN);
-        converted += op_count(c == LZF_ENT_CONVERTED);
-        unchanged += op_count(c == LZF_ENT_UNCHANGED);
+        done += sd_count(c == LZF_ENT_DONE);
+        expired += sd_count(c == LZF_ENT_EXPIRED);
+        locked += sd_count(c == LZF_ENT_LOCKED);
+        nan += sd_count(c == LZF_ENT_NAN);
+        converted += sd_count(c == LZF_ENT_CONVERTED);
+        unchanged += sd_count(c == LZF_ENT_UNCHANGED);
     }
-    if ((threadIdx.x & 63u) != 0u) return;
-    unsigned long long *r = (unsigned long long *)a.result;
-    const uint32_t found = done + converted + unchanged;
-    if (found) atomicAdd(r, (unsigned long long)found);
-    if (expired) atomicAdd(r + 1, (unsigned long long)expired);
-    if (locked) atomicAdd(r + 2, (unsigned long long)locked);
-    if (nan) atomicAdd(r + 3, (unsigned long long)nan);
-    if (converted) atomicAdd(r + 4, (unsigned long long)converted);
-    if (unchanged) atomicAdd(r + 5, (unsigned long long)unchanged);
+    sd_leader_add(a.result, done + converted + unchanged);
+    sd_leader_add(a.result + 1, expired);
+    sd_leader_add(a.result + 2, locked);
+    sd_leader_add(a.result + 3, nan);
+    sd_leader_add(a.result + 4, converted);
+    sd_leader_add(a.result + 5, unchanged);
 }
 
 /* ---- set_guard ---------------------------------------------------------------- */
@@ -287,33 +247,25 @@ __global__ __launch_bounds__(OP_BLOCK) void lzf_minc_apply_kernel(LzfMincArgs a)
  * the batch that is not dead and is locked keeps the key, and the new item
  * dies.  No validity test, as in the reference.  The occupants read lie
  * outside [first, first + n), the items written inside it */
-__global__ __launch_bounds__(OP_BLOCK) void lzf_store_set_guard_kernel(const uint32_t *__restrict__ occ, uint32_t first,
-                                                                       uint32_t n, uint8_t *enc, uint32_t count,
-                                                                       const int64_t *item_time,
-                                                                       const int64_t *item_lock, int64_t now,
-                                                                       uint8_t *refused, uint64_t *result)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_set_guard_kernel(const uint32_t *__restrict__ occ, uint32_t first,
+                                                                       uint32_t n, LzfItems it, uint8_t *refused,
+                                                                       uint64_t *result)
 {
-    const uint64_t step = (uint64_t)gridDim.x * OP_BLOCK;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint32_t hits = 0u;
-    for (uint64_t b = (uint64_t)blockIdx.x * OP_BLOCK; b < n; b += step) {
+    for (uint64_t b = (uint64_t)blockIdx.x * SD_BLOCK; b < n; b += step) {
         const uint64_t k = b + threadIdx.x;
         bool refuse = false;
         if (k < n) {
             const uint32_t j = occ[k];
             const bool inside = j >= first && (uint64_t)j < (uint64_t)first + n;
-            refuse = j < count && !inside && enc[j] != (uint8_t)LZF_ENC_NULL && mg_locked(j, item_time, item_lock, now);
-            if (refuse) enc[first + k] = (uint8_t)LZF_ENC_NULL;
+            refuse = j < it.count && !inside && it.enc[j] != (uint8_t)LZF_ENC_NULL && mg_locked(j, it);
+            if (refuse) it.enc[first + k] = (uint8_t)LZF_ENC_NULL;
             if (refused) refused[k] = refuse ? 1u : 0u;
         }
-        hits += op_count(refuse);
+        hits += sd_count(refuse);
     }
-    if ((threadIdx.x & 63u) == 0u && hits) atomicAdd((unsigned long long *)result, (unsigned long long)hits);
-}
-
-static inline uint32_t op_sweep_grid(uint64_t n)
-{
-    const uint64_t g = (n + OP_BLOCK - 1u) / OP_BLOCK;
-    return (uint32_t)(g < OP_GRID ? g : OP_GRID);
+    sd_leader_add(result, hits);
 }
 
 template <int OP>
@@ -321,7 +273,7 @@ hipError_t op_launch_lock(const LzfLockArgs &a, uint32_t words, hipStream_t s)
 {
     const hipError_t e = hipMemsetAsync(a.result, 0, words * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lzf_store_lock_kernel<OP>, dim3(op_sweep_grid(a.n)), dim3(OP_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_store_lock_kernel<OP>, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
@@ -342,41 +294,24 @@ hipError_t lzf_launch_store_mdel(const LzfLockArgs &a, hipStream_t s)
     return op_launch_lock<OP_MDEL>(a, 3u, s);
 }
 
-uint64_t lzf_minc_work_bytes(uint32_t n)
-{
-    /* state (8 x u64) | the new numbers (i64) | tile counts (u64 per tile) |
-     * the classes (u8); room to align the caller's pointer.  Below 2^36 */
-    return 64u + (uint64_t)n * 9u + (uint64_t)op_tiles(n) * 8u + 16u;
-}
-
-void lzf_minc_carve(LzfMincArgs &a, void *work)
-{
-    uint8_t *w = (uint8_t *)(((uintptr_t)work + 7u) & ~(uintptr_t)7u);
-    a.w_state = (uint64_t *)w;            w += 64;
-    a.w_val = (int64_t *)w;               w += (size_t)a.n * 8;
-    a.w_tile = (uint64_t *)w;             w += (size_t)op_tiles(a.n) * 8;
-    a.w_cls = w;
-}
-
 hipError_t lzf_launch_store_minc(LzfMincArgs &a, hipStream_t s)
 {
     const hipError_t e = hipMemsetAsync(a.result, 0, 6 * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    const uint32_t nt = op_tiles(a.n);
-    hipLaunchKernelGGL(lzf_minc_classify_kernel, dim3(nt), dim3(OP_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(lzf_minc_scan_kernel, dim3(1), dim3(OP_BLOCK), 0, s, a, nt);
-    hipLaunchKernelGGL(lzf_minc_apply_kernel, dim3(nt), dim3(OP_BLOCK), 0, s, a);
+    const uint32_t nt = sd_tiles(a.n);
+    hipLaunchKernelGGL(lzf_minc_classify_kernel, dim3(nt), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_minc_scan_kernel, dim3(1), dim3(SD_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_minc_apply_kernel, dim3(nt), dim3(SD_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t lzf_launch_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, uint8_t *enc, uint32_t count,
-                                      const int64_t *item_time, const int64_t *item_lock, int64_t now,
+hipError_t lzf_launch_store_set_guard(const uint32_t *occ, uint32_t first, uint32_t n, const LzfItems &it,
                                       uint8_t *refused, uint64_t *result, hipStream_t s)
 {
     const hipError_t e = hipMemsetAsync(result, 0, sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lzf_store_set_guard_kernel, dim3(op_sweep_grid(n)), dim3(OP_BLOCK), 0, s, occ, first, n, enc,
-                       count, item_time, item_lock, now, refused, result);
+    hipLaunchKernelGGL(lzf_store_set_guard_kernel, dim3(sd_sweep_grid(n)), dim3(SD_BLOCK), 0, s, occ, first, n, it,
+                       refused, result);
     return hipGetLastError();
 }
 

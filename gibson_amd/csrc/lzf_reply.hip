@@ -35,60 +35,46 @@
  * of this translation unit, not part of the library's routed kernel set: they
  * have internal linkage (anonymous namespace).
  */
-#include "lzf_dev.h"
+#include "lzf_store_dev.h"
 #include "../../include/lzf_gpu.h"
 
-#define RP_BLOCK 256u
-#define RP_PER   4u
-#define RP_TILE  (RP_BLOCK * RP_PER)      /* entries per tile */
-#define RP_WAVES (RP_BLOCK / 64u)
-#define RP_GRID  2048u                    /* the check: 256 CUs x 8 workgroups */
-#define RP_PAD   0xFFFFFFFFu
-/* the write kernel works a wave per entry, RP_WAVES entries per workgroup: the
- * cap of its grid, past which the waves stride over the list */
-#define RP_WRITE_GRID 16384u
-#define RP_HDR   7u                       /* [i16 code][u8 encoding][u32 size] */
-#define RP_CODE  8u                       /* a code reply: the header and one 0x00 byte */
+/* the geometry, the scans and the byte helpers: lzf_store_dev.h */
+#define RP_CODE  (SD_HDR + 1u)            /* a code reply: the header and one 0x00 byte */
 /* g_cls of an entry the decoder has nothing to do for */
 #define RP_NO_CLASS 0xFFu
-
-static inline uint32_t rp_tiles(uint32_t n)
-{
-    return (uint32_t)(((uint64_t)n + RP_TILE - 1u) / RP_TILE);
-}
 
 namespace {
 
 enum { RP_STATUS = 0 };                   /* state words of the work area */
 
-/* a tile's four counts in one word: each is at most RP_TILE = 2^10 */
+/* a tile's four counts in one word: each is at most SD_TILE = 2^10 */
 #define RP_ONE_VALUE   1ull
 #define RP_ONE_EXPIRED (1ull << 16)
 #define RP_ONE_SKIPPED (1ull << 32)
 #define RP_ONE_REFUSED (1ull << 48)
 #define RP_CNT_MASK    0xFFFFull
 
-/* thread t of a tile takes entries t * RP_PER .. + RP_PER, so the scan over the
+/* thread t of a tile takes entries t * SD_PER .. + SD_PER, so the scan over the
  * threads is the scan over the list */
-__global__ __launch_bounds__(RP_BLOCK) void lzf_reply_classify_kernel(LzfReplyArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_reply_classify_kernel(LzfReplyArgs a)
 {
-    __shared__ uint64_t sw[RP_WAVES];
-    const uint64_t first = (uint64_t)blockIdx.x * RP_TILE + threadIdx.x * RP_PER;
-    uint64_t sz[RP_PER], s = 0ull, cnt = 0ull;
+    __shared__ uint64_t sw[SD_WAVES];
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
+    uint64_t sz[SD_PER], s = 0ull, cnt = 0ull;
 #pragma unroll
-    for (uint32_t j = 0; j < RP_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         const uint64_t k = first + j;
         sz[j] = 0ull;
         if (k >= a.n) continue;
         const uint32_t i = a.idx[k];
         int code, st;
-        uint32_t dead = RP_PAD;
+        uint32_t dead = SD_PAD;
         if (a.mode == LZF_REPLY_GET) {
-            const int v = mg_validity(i, a.count, a.enc, a.item_time, a.item_ttl, a.now);
+            const int v = mg_validity(i, a.it);
             if (v == MG_VALID) {
                 code = LZF_REPL_VAL;
                 st = LZF_ENT_DONE;
-                if (a.last_access) a.last_access[i] = a.now;   /* src/query.c:650 */
+                if (a.it.last_access) a.it.last_access[i] = a.it.now;   /* src/query.c:650 */
             } else {
                 code = LZF_REPL_ERR_NOT_FOUND;                 /* src/query.c:659 */
                 st = v == MG_EXPIRED ? LZF_ENT_EXPIRED : LZF_ENT_DEAD;
@@ -98,7 +84,7 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_classify_kernel(LzfReplyAr
         } else {
             st = a.op_status[k];
             code = lzf_reply_code_of(st);
-            if (code == LZF_REPL_VAL && (i >= a.count || a.enc[i] == (uint8_t)LZF_ENC_NULL)) code = LZF_REPL_ERR;
+            if (code == LZF_REPL_VAL && (i >= a.it.count || a.it.enc[i] == (uint8_t)LZF_ENC_NULL)) code = LZF_REPL_ERR;
             if (code != LZF_REPL_VAL) cnt += RP_ONE_SKIPPED;
         }
         uint8_t e = (uint8_t)LZF_ENC_NULL, cls = (uint8_t)RP_NO_CLASS;
@@ -106,7 +92,7 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_classify_kernel(LzfReplyAr
         uint32_t vs = 0u, vl = 0u;
         sz[j] = RP_CODE;
         if (code == LZF_REPL_VAL) {
-            e = a.enc[i];
+            e = a.it.enc[i];
             vo = a.val_off[i];
             vs = a.val_size[i];
             vl = e == (uint8_t)LZF_ENC_LZF ? a.val_len[i] : vs;
@@ -120,7 +106,7 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_classify_kernel(LzfReplyAr
                 vl = 0u;
                 cnt += RP_ONE_REFUSED;
             } else {
-                const uint64_t whole = (uint64_t)RP_HDR + vl;
+                const uint64_t whole = (uint64_t)SD_HDR + vl;
                 sz[j] = whole < RP_CODE ? (uint64_t)RP_CODE : whole;
                 cnt += RP_ONE_VALUE;
             }
@@ -136,10 +122,10 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_classify_kernel(LzfReplyAr
         s += sz[j];
     }
     uint64_t tot, ctot;
-    uint64_t o = dv_block_excl<RP_WAVES>(s, sw, &tot);
-    (void)dv_block_excl<RP_WAVES>(cnt, sw, &ctot);
+    uint64_t o = dv_block_excl<SD_WAVES>(s, sw, &tot);
+    (void)dv_block_excl<SD_WAVES>(cnt, sw, &ctot);
 #pragma unroll
-    for (uint32_t j = 0; j < RP_PER; j++) {
+    for (uint32_t j = 0; j < SD_PER; j++) {
         if (first + j < a.n) a.w_off[first + j] = o;
         o += sz[j];
     }
@@ -152,19 +138,19 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_classify_kernel(LzfReplyAr
 /* one workgroup: the exclusive scan of the tiles' slot bytes in place (8 tile
  * sums per thread, as the select's carry), the four counts, and the call's
  * decision */
-__global__ __launch_bounds__(RP_BLOCK) void lzf_reply_scan_kernel(LzfReplyArgs a, uint32_t ntile)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_reply_scan_kernel(LzfReplyArgs a, uint32_t ntile)
 {
-    __shared__ uint64_t sw[RP_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     uint64_t c[4] = {0ull, 0ull, 0ull, 0ull};
-    for (uint32_t t = threadIdx.x; t < ntile; t += RP_BLOCK) {
+    for (uint32_t t = threadIdx.x; t < ntile; t += SD_BLOCK) {
         const uint64_t cn = a.w_tcnt[t];
 #pragma unroll
         for (uint32_t q = 0; q < 4u; q++) c[q] += (cn >> (16u * q)) & RP_CNT_MASK;
     }
     uint64_t tot[4];
 #pragma unroll
-    for (uint32_t q = 0; q < 4u; q++) (void)dv_block_excl<RP_WAVES>(c[q], sw, &tot[q]);
-    const uint64_t need = dv_carry_scan<RP_WAVES>(a.w_tile, ntile, sw);
+    for (uint32_t q = 0; q < 4u; q++) (void)dv_block_excl<SD_WAVES>(c[q], sw, &tot[q]);
+    const uint64_t need = dv_carry_scan<SD_WAVES>(a.w_tile, ntile, sw);
     if (threadIdx.x != 0u) return;
     const uint64_t st = need > a.rep_cap ? LZF_REPLY_TOO_BIG : LZF_REPLY_OK;
     a.w_state[RP_STATUS] = st;
@@ -177,63 +163,43 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_scan_kernel(LzfReplyArgs a
     *a.rep_used = st == (uint64_t)LZF_REPLY_OK ? need : 0ull;
 }
 
-__device__ inline void rp_put32(uint8_t *p, uint32_t x)
-{
-    p[0] = (uint8_t)x; p[1] = (uint8_t)(x >> 8); p[2] = (uint8_t)(x >> 16); p[3] = (uint8_t)(x >> 24);
-}
-
 /* gbClientEnqueueCode's reply (src/net.c:1204-1214): size 1, one 0x00 byte */
 __device__ inline void rp_put_code(uint8_t *f, int code)
 {
-    f[0] = (uint8_t)code; f[1] = (uint8_t)((uint32_t)code >> 8);      /* src/net.c:1185 */
-    f[2] = (uint8_t)LZF_ENC_PLAIN;
-    rp_put32(f + 3, 1u);
-    f[7] = 0u;
+    sd_put_header(f, code, (uint8_t)LZF_ENC_PLAIN, 1u);
+    f[SD_HDR] = 0u;
 }
 
 /* one wave per entry, the waves striding over the list.  nskip: the number of
  * skip lists (one per decode class, or one for all of them) */
-__global__ __launch_bounds__(RP_BLOCK) void lzf_reply_write_kernel(LzfReplyArgs a, uint32_t nskip)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_reply_write_kernel(LzfReplyArgs a, uint32_t nskip)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const bool go = a.w_state[RP_STATUS] == (uint64_t)LZF_REPLY_OK;
-    const uint64_t w0 = (uint64_t)blockIdx.x * RP_WAVES + (threadIdx.x >> 6), step = (uint64_t)gridDim.x * RP_WAVES;
+    const uint64_t w0 = (uint64_t)blockIdx.x * SD_WAVES + (threadIdx.x >> 6), step = (uint64_t)gridDim.x * SD_WAVES;
     for (uint64_t k = w0; k < a.n; k += step) {
         /* whatever the status: the reference's validity pass runs before the reply is built */
         const uint32_t dead = a.g_null[k];
-        if (dead != RP_PAD && lane == 0u) a.enc[dead] = (uint8_t)LZF_ENC_NULL;
+        if (dead != SD_PAD && lane == 0u) a.it.enc[dead] = (uint8_t)LZF_ENC_NULL;
         const uint8_t e = a.g_enc[k];
         const int code = a.g_code[k];
         const uint32_t vl = a.g_val_len[k];
-        const uint64_t off = a.w_off[k] + a.w_tile[k / RP_TILE];
+        const uint64_t off = a.w_off[k] + a.w_tile[k / SD_TILE];
         const bool dec = go && a.g_cls[k] != (uint8_t)RP_NO_CLASS;
         if (go) {
             uint8_t *f = a.replies + off;
             if (code != LZF_REPL_VAL) {
                 if (lane == 0u) rp_put_code(f, code);
             } else {
-                if (lane == 0u) {
-                    f[0] = (uint8_t)LZF_REPL_VAL; f[1] = 0u;
-                    f[2] = e == (uint8_t)LZF_ENC_LZF ? (uint8_t)LZF_ENC_PLAIN : e;   /* src/net.c:1233, :1250 */
-                    rp_put32(f + 3, vl);
-                }
-                if (e != (uint8_t)LZF_ENC_LZF) {
-                    /* 16 bytes per lane (unaligned loads and stores), then the tail */
-                    const uint8_t *s = a.store + a.g_val_off[k];
-                    uint8_t *v = f + RP_HDR;
-                    const uint32_t whole = vl & ~15u;
-                    for (uint32_t j = lane * 16u; j < whole; j += 64u * 16u) {
-                        const uint4 x = dv_ld16(s + j);
-                        __builtin_memcpy(v + j, &x, 16);
-                    }
-                    for (uint32_t j = whole + lane; j < vl; j += 64u) v[j] = s[j];
-                }
+                if (lane == 0u)                                                   /* src/net.c:1233, :1250 */
+                    sd_put_header(f, LZF_REPL_VAL, e == (uint8_t)LZF_ENC_LZF ? (uint8_t)LZF_ENC_PLAIN : e, vl);
+                if (e != (uint8_t)LZF_ENC_LZF) sd_wave_copy(f + SD_HDR, a.store + a.g_val_off[k], vl, lane);
             }
         }
         if (lane == 0u) {
             a.rep_off[k] = off;
-            a.rep_len[k] = code == LZF_REPL_VAL ? RP_HDR + vl : RP_CODE;
-            a.w_voff[k] = off + RP_HDR;
+            a.rep_len[k] = code == LZF_REPL_VAL ? SD_HDR + vl : RP_CODE;
+            a.w_voff[k] = off + SD_HDR;
             const uint32_t cls = nskip == 1u ? 0u : a.g_cls[k];
             for (uint32_t c = 0; c < nskip; c++) a.w_skip[(uint64_t)c * a.n + k] = dec && cls == c ? 0u : 1u;
         }
@@ -243,13 +209,13 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_write_kernel(LzfReplyArgs 
 /* every LZF entry must have decoded to its recorded length; one that did not
  * gets the REPL_ERR code reply at the start of its slot.  By the whole grid,
  * the failures summed per workgroup and added with one atomic per workgroup */
-__global__ __launch_bounds__(RP_BLOCK) void lzf_reply_check_kernel(LzfReplyArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_reply_check_kernel(LzfReplyArgs a)
 {
-    __shared__ uint64_t sw[RP_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     if (a.w_state[RP_STATUS] != (uint64_t)LZF_REPLY_OK) return;   /* nothing was decoded; the same for every thread */
-    const uint64_t step = (uint64_t)gridDim.x * RP_BLOCK;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint64_t bad = 0ull;
-    for (uint64_t k = (uint64_t)blockIdx.x * RP_BLOCK + threadIdx.x; k < a.n; k += step) {
+    for (uint64_t k = (uint64_t)blockIdx.x * SD_BLOCK + threadIdx.x; k < a.n; k += step) {
         if (a.g_cls[k] == (uint8_t)RP_NO_CLASS) continue;
         if (a.w_err[k] == 0 && a.w_len[k] == a.g_val_len[k]) continue;
         rp_put_code(a.replies + a.rep_off[k], LZF_REPL_ERR);
@@ -258,7 +224,7 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_check_kernel(LzfReplyArgs 
         bad++;
     }
     uint64_t tot;
-    (void)dv_block_excl<RP_WAVES>(bad, sw, &tot);
+    (void)dv_block_excl<SD_WAVES>(bad, sw, &tot);
     if (threadIdx.x == 0u && tot) {
         atomicAdd((unsigned long long *)&a.result[5], (unsigned long long)tot);
         atomicAdd((unsigned long long *)&a.result[0], 0ull - (unsigned long long)tot);
@@ -267,68 +233,27 @@ __global__ __launch_bounds__(RP_BLOCK) void lzf_reply_check_kernel(LzfReplyArgs 
 
 }  // namespace
 
-uint64_t lzf_reply_work_bytes(uint32_t n)
-{
-    /* state (8 x u64) | val_off, off, voff (u64) | tile bytes, tile counts (u64
-     * per tile) | val_size, val_len, null, len, err (u32) | enc, code, cls and
-     * the skip lists (u8); room to align the caller's pointer.  Below 2^38 */
-    return 64u + (uint64_t)n * (3u * 8u + 5u * 4u + 3u + LZF_DECODE_NCLASS) + (uint64_t)rp_tiles(n) * 16u + 16u;
-}
-
-void lzf_reply_carve(LzfReplyArgs &a, void *work)
-{
-    uint8_t *w = (uint8_t *)(((uintptr_t)work + 7u) & ~(uintptr_t)7u);
-    const size_t n = a.n, nt = rp_tiles(a.n);
-    a.w_state = (uint64_t *)w;            w += 64;
-    a.g_val_off = (uint64_t *)w;          w += n * 8;
-    a.w_off = (uint64_t *)w;              w += n * 8;
-    a.w_voff = (uint64_t *)w;             w += n * 8;
-    a.w_tile = (uint64_t *)w;             w += nt * 8;
-    a.w_tcnt = (uint64_t *)w;             w += nt * 8;
-    a.g_val_size = (uint32_t *)w;         w += n * 4;
-    a.g_val_len = (uint32_t *)w;          w += n * 4;
-    a.g_null = (uint32_t *)w;             w += n * 4;
-    a.w_len = (uint32_t *)w;              w += n * 4;
-    a.w_err = (int32_t *)w;               w += n * 4;
-    a.g_enc = w;                          w += n;
-    a.g_code = w;                         w += n;
-    a.g_cls = w;                          w += n;
-    a.w_skip = w;                         /* LZF_DECODE_NCLASS lists of n */
-}
-
 hipError_t lzf_launch_store_replies(LzfReplyArgs &a, hipStream_t s,
                                     hipError_t (*decode)(const LzfBatch &, hipStream_t), bool one_route)
 {
-    const uint32_t nt = rp_tiles(a.n);
+    const uint32_t nt = sd_tiles(a.n);
     /* the classes that can hold an entry: those whose sizes begin at or below
      * the call's bound */
     uint32_t nclass = 1u;
     while (!one_route && nclass < LZF_DECODE_NCLASS && a.max_val_len > lzf_decode_class_edge(nclass - 1u)) nclass++;
-    hipLaunchKernelGGL(lzf_reply_classify_kernel, dim3(nt), dim3(RP_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(lzf_reply_scan_kernel, dim3(1), dim3(RP_BLOCK), 0, s, a, nt);
-    const uint64_t nw = ((uint64_t)a.n + RP_WAVES - 1u) / RP_WAVES;
-    hipLaunchKernelGGL(lzf_reply_write_kernel, dim3((uint32_t)(nw < RP_WRITE_GRID ? nw : RP_WRITE_GRID)), dim3(RP_BLOCK),
-                       0, s, a, nclass);
+    hipLaunchKernelGGL(lzf_reply_classify_kernel, dim3(nt), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_reply_scan_kernel, dim3(1), dim3(SD_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_reply_write_kernel, dim3(sd_wave_grid(a.n)), dim3(SD_BLOCK), 0, s, a, nclass);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    LzfBatch b{};
-    b.in = a.store;
-    b.in_off = a.g_val_off;
-    b.in_len = a.g_val_size;
-    b.out = a.replies;
-    b.out_off = a.w_voff;
-    b.out_cap = a.g_val_len;
-    b.out_len = a.w_len;
-    b.err = a.w_err;
-    b.count = a.n;
     for (uint32_t c = 0; c < nclass; c++) {
         const uint32_t edge = one_route ? 0xFFFFFFFFu : lzf_decode_class_edge(c);
-        b.max_len = edge < a.max_val_len ? edge : a.max_val_len;
-        b.skip = a.w_skip + (size_t)c * a.n;
+        const LzfBatch b = sd_decode_batch(a.store, a.g_val_off, a.g_val_size, a.replies, a.w_voff, a.g_val_len, a.w_len,
+                                           a.w_err, a.n, edge < a.max_val_len ? edge : a.max_val_len,
+                                           a.w_skip + (size_t)c * a.n);
         if ((e = decode(b, s)) != hipSuccess) return e;
     }
-    const uint64_t g = ((uint64_t)a.n + RP_BLOCK - 1u) / RP_BLOCK;
-    hipLaunchKernelGGL(lzf_reply_check_kernel, dim3((uint32_t)(g < RP_GRID ? g : RP_GRID)), dim3(RP_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_reply_check_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -57,15 +57,13 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "lzf_dev.h"
+#include "lzf_store_dev.h"
 #include "gb_policy.h"
 #include "../../include/lzf_gpu.h"
 
-#define ST_BLOCK 256u
-#define ST_PER   4u
-#define ST_TILE  (ST_BLOCK * ST_PER)      /* values per scan tile */
-#define ST_WAVES (ST_BLOCK / 64u)
-/* destination bytes per pack tile (a multiple of 16 * ST_BLOCK = 4096, so
+/* The scans and sweeps run on the toolkit's geometry (lzf_store_dev.h).  The
+ * pack kernel's own: it is balanced by destination bytes, not by entries.
+ * Destination bytes per pack tile (a multiple of 16 * SD_BLOCK = 4096, so
  * every lane of a workgroup has the same number of granules).  256 K x 4 KiB
  * json, 500 MB packed: the pack kernel takes 467 us at 16 KiB and 300 us at
  * 64 KiB (a plain copy of the same bytes: 184 us); 4 KiB is slower again and
@@ -74,18 +72,6 @@
  * would sit on few workgroups */
 #define ST_PACK_TILE 65536u
 #define ST_PACK_GRID 2048u                /* 256 CUs x 8 workgroups */
-
-static inline uint32_t st_tiles(uint32_t count)
-{
-    return (uint32_t)(((uint64_t)count + ST_TILE - 1u) / ST_TILE);
-}
-
-/* the scratch slots' room: in_bytes + 8 * count, saturating */
-static __host__ __device__ inline uint64_t st_slot_room(uint64_t in_bytes, uint32_t count)
-{
-    const uint64_t r = in_bytes + 8ull * count;
-    return r < in_bytes ? ~0ull : r;
-}
 
 namespace {
 
@@ -107,38 +93,30 @@ __device__ inline uint64_t st_item(const LzfStoreArgs &a, uint64_t i, bool ework
 }
 
 template <bool SIZE>
-__global__ __launch_bounds__(ST_BLOCK) void lzf_store_reduce_kernel(LzfStoreArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_reduce_kernel(LzfStoreArgs a)
 {
-    __shared__ uint64_t sw[ST_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     const bool ework = SIZE && a.w_state[ST_EWORK] != 0ull;
-    const uint64_t first = (uint64_t)blockIdx.x * ST_TILE + threadIdx.x * ST_PER;
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
     uint64_t s = 0ull;
 #pragma unroll
-    for (uint32_t k = 0; k < ST_PER; k++)
+    for (uint32_t k = 0; k < SD_PER; k++)
         if (first + k < a.count) s += st_item<SIZE>(a, first + k, ework);
     uint64_t tot;
-    (void)dv_block_excl<ST_WAVES>(s, sw, &tot);
+    (void)dv_block_excl<SD_WAVES>(s, sw, &tot);
     if (threadIdx.x == 0u) a.w_tile[blockIdx.x] = tot;
 }
 
-/* one workgroup: the exclusive scan of the tile sums in place, in pieces of
- * ST_BLOCK with a running carry, and the batch-wide decision */
+/* one workgroup: the exclusive scan of the tile sums in place, and the
+ * batch-wide decision */
 template <bool SIZE>
-__global__ __launch_bounds__(ST_BLOCK) void lzf_store_carry_kernel(LzfStoreArgs a, uint32_t ntile)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_carry_kernel(LzfStoreArgs a, uint32_t ntile)
 {
-    __shared__ uint64_t sw[ST_WAVES];
-    uint64_t run = 0ull;
-    for (uint32_t c = 0; c < ntile; c += ST_BLOCK) {
-        const uint32_t i = c + threadIdx.x;
-        const uint64_t x = i < ntile ? a.w_tile[i] : 0ull;
-        uint64_t tot;
-        const uint64_t o = dv_block_excl<ST_WAVES>(x, sw, &tot);
-        if (i < ntile) a.w_tile[i] = run + o;
-        run += tot;
-    }
+    __shared__ uint64_t sw[SD_WAVES];
+    const uint64_t run = dv_carry_scan<SD_WAVES>(a.w_tile, ntile, sw);
     if (threadIdx.x != 0u) return;
     if (!SIZE) {
-        a.w_state[ST_EWORK] = run > st_slot_room(a.in_bytes, a.count) ? 1ull : 0ull;
+        a.w_state[ST_EWORK] = run > sd_slot_room(a.in_bytes, a.count) ? 1ull : 0ull;
         return;
     }
     const uint64_t base = *a.store_used, end = base + run;
@@ -153,23 +131,23 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_store_carry_kernel(LzfStoreArgs 
 }
 
 template <bool SIZE>
-__global__ __launch_bounds__(ST_BLOCK) void lzf_store_write_kernel(LzfStoreArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_write_kernel(LzfStoreArgs a)
 {
-    __shared__ uint64_t sw[ST_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     const bool ework = a.w_state[ST_EWORK] != 0ull;
     const bool refused = SIZE && a.w_state[ST_STATUS] != 0ull;
-    const uint64_t first = (uint64_t)blockIdx.x * ST_TILE + threadIdx.x * ST_PER;
-    uint64_t v[ST_PER], s = 0ull;
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
+    uint64_t v[SD_PER], s = 0ull;
 #pragma unroll
-    for (uint32_t k = 0; k < ST_PER; k++) {
+    for (uint32_t k = 0; k < SD_PER; k++) {
         v[k] = first + k < a.count ? st_item<SIZE>(a, first + k, ework) : 0ull;
         s += v[k];
     }
     uint64_t tot;
-    uint64_t o = dv_block_excl<ST_WAVES>(s, sw, &tot) + a.w_tile[blockIdx.x];
+    uint64_t o = dv_block_excl<SD_WAVES>(s, sw, &tot) + a.w_tile[blockIdx.x];
     if (SIZE) o += a.w_state[ST_BASE];
 #pragma unroll
-    for (uint32_t k = 0; k < ST_PER; k++) {
+    for (uint32_t k = 0; k < SD_PER; k++) {
         const uint64_t i = first + k;
         if (i >= a.count) break;
         if (SIZE) {
@@ -201,18 +179,18 @@ __device__ inline uint32_t st_find(const uint64_t *__restrict__ off, uint32_t lo
     return lo;
 }
 
-/* how many threads of the workgroup say yes; sc: ST_WAVES words of LDS */
+/* how many threads of the workgroup say yes; sc: SD_WAVES words of LDS */
 __device__ inline uint32_t st_block_count(uint32_t wave_yes, uint32_t *sc)
 {
     if ((threadIdx.x & 63u) == 0u) sc[threadIdx.x >> 6] = wave_yes;
     __syncthreads();
     uint32_t n = 0u;
-    for (uint32_t w = 0; w < ST_WAVES; w++) n += sc[w];
+    for (uint32_t w = 0; w < SD_WAVES; w++) n += sc[w];
     __syncthreads();
     return n;
 }
 
-/* st_find by the whole workgroup: every round the threads probe ST_BLOCK
+/* st_find by the whole workgroup: every round the threads probe SD_BLOCK
  * evenly spaced entries of [lo, hi) at once and the range shrinks to one
  * stride, so 2^32 entries take four dependent loads, not 32.  The same
  * result in every thread */
@@ -220,7 +198,7 @@ __device__ inline uint32_t st_find_block(const uint64_t *__restrict__ off, uint3
                                          uint32_t *sc)
 {
     while (hi - lo > 1u) {
-        const uint32_t step = (uint32_t)(((uint64_t)(hi - lo) + ST_BLOCK - 1u) / ST_BLOCK);
+        const uint32_t step = (uint32_t)(((uint64_t)(hi - lo) + SD_BLOCK - 1u) / SD_BLOCK);
         const uint64_t i = lo + (uint64_t)threadIdx.x * step;
         const bool yes = i < hi && off[i] <= p;       /* true for the threads up to the one that holds p */
         const uint32_t c = st_block_count((uint32_t)__popcll(__ballot(yes)), sc);
@@ -248,13 +226,6 @@ __device__ inline uint4 st_ld16_realign(const uint8_t *s)
     const uint32_t x4 = ws == 0u ? b.x : ws == 1u ? b.y : ws == 2u ? b.z : b.w;
     return make_uint4(__builtin_amdgcn_alignbyte(x1, x0, sh), __builtin_amdgcn_alignbyte(x2, x1, sh),
                       __builtin_amdgcn_alignbyte(x3, x2, sh), __builtin_amdgcn_alignbyte(x4, x3, sh));
-}
-
-__device__ inline uint4 st_ld16(const uint8_t *s)
-{
-    uint4 v;
-    __builtin_memcpy(&v, s, 16);
-    return v;
 }
 
 /* where value i's stored bytes come from, as one word: the offset in the
@@ -358,12 +329,12 @@ __device__ inline void st_pack_edge(uint8_t *store, const Map &m, uint64_t sa, u
 template <bool REALIGN, bool EDGES, typename Map>
 __device__ inline void st_pack_tile(uint8_t *store, const Map &m, uint64_t sa, uint64_t ta, uint64_t lo, uint64_t hi)
 {
-    for (uint64_t gb = ta + 16ull * threadIdx.x; gb < hi; gb += 64ull * ST_BLOCK) {
+    for (uint64_t gb = ta + 16ull * threadIdx.x; gb < hi; gb += 64ull * SD_BLOCK) {
         uint4 v[4];
         uint32_t how[4];               /* 0: nothing, 1: v is the granule, 2: not inside one value */
 #pragma unroll
         for (uint32_t u = 0; u < 4u; u++) {
-            const uint64_t g = gb + 16ull * ST_BLOCK * u;
+            const uint64_t g = gb + 16ull * SD_BLOCK * u;
             how[u] = 0u;
             if (g < lo || g + 16u > hi) {                 /* a partial granule, or past the tile */
                 if (g + 16u > lo && g < hi) how[u] = 2u;
@@ -377,16 +348,16 @@ __device__ inline void st_pack_tile(uint8_t *store, const Map &m, uint64_t sa, u
                 continue;
             }
             const uint8_t *s = src + (g - sa - vo);
-            v[u] = REALIGN ? st_ld16_realign(s) : st_ld16(s);
+            v[u] = REALIGN ? st_ld16_realign(s) : dv_ld16(s);
             how[u] = 1u;
         }
 #pragma unroll
         for (uint32_t u = 0; u < 4u; u++)
-            if (how[u] == 1u) *(uint4 *)(store + (gb + 16ull * ST_BLOCK * u - sa)) = v[u];
+            if (how[u] == 1u) *(uint4 *)(store + (gb + 16ull * SD_BLOCK * u - sa)) = v[u];
         if (EDGES) {
 #pragma unroll
             for (uint32_t u = 0; u < 4u; u++)
-                if (how[u] == 2u) st_pack_edge(store, m, sa, gb + 16ull * ST_BLOCK * u, lo, hi);
+                if (how[u] == 2u) st_pack_edge(store, m, sa, gb + 16ull * SD_BLOCK * u, lo, hi);
         }
     }
 }
@@ -396,10 +367,10 @@ __device__ inline void st_pack_tile(uint8_t *store, const Map &m, uint64_t sa, u
 #define ST_LDS_VALS 512u
 
 template <bool REALIGN, typename P>
-__global__ __launch_bounds__(ST_BLOCK) void lzf_store_pack_kernel(P p, uint32_t tile)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_pack_kernel(P p, uint32_t tile)
 {
     __shared__ uint64_t s_off[ST_LDS_VALS + 1u], s_from[ST_LDS_VALS];
-    __shared__ uint32_t sc[ST_WAVES];
+    __shared__ uint32_t sc[SD_WAVES];
     const uint64_t total = p.total();
     if (!total) return;                                   /* refused, or nothing to store */
     /* absolute addresses: the packed range [d0, d1), tiles from a0 (which may
@@ -420,7 +391,7 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_store_pack_kernel(P p, uint32_t 
          * them start at or before the tile's last byte -- the tile's values
          * [i0, i0 + n), entry n being the end of the last one */
         uint32_t yes = 0u;
-        for (uint32_t k = threadIdx.x; k < ST_LDS_VALS + ST_BLOCK; k += ST_BLOCK) {
+        for (uint32_t k = threadIdx.x; k < ST_LDS_VALS + SD_BLOCK; k += SD_BLOCK) {
             const uint64_t i = (uint64_t)i0 + k;
             const bool in = k <= ST_LDS_VALS && i < count;
             const uint64_t o = in ? voff[i] : d1 - sa;
@@ -441,7 +412,7 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_store_pack_kernel(P p, uint32_t 
          * multiple of 16: one lane per cut, so a wave works on 64 of them at
          * once.  Cuts in one granule are neighbours in the table: the first
          * takes the granule */
-        for (uint32_t k = threadIdx.x; k <= n; k += ST_BLOCK) {
+        for (uint32_t k = threadIdx.x; k <= n; k += SD_BLOCK) {
             const uint64_t c = sa + s_off[k];
             if (!(c & 15ull) || c < lo || c > hi) continue;
             const uint64_t g = c & ~15ull;
@@ -477,14 +448,14 @@ enum { ST_NLIVE = 4 };
 /* RANGE: also fold whether a live item's [val_off, val_off + val_size) leaves
  * [0, src_cap) (usage has no offsets to check) */
 template <bool RANGE>
-__global__ __launch_bounds__(ST_BLOCK) void lzf_compact_reduce_kernel(LzfCompactArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_compact_reduce_kernel(LzfCompactArgs a)
 {
-    __shared__ uint64_t sw[ST_WAVES];
-    const uint64_t first = (uint64_t)blockIdx.x * ST_TILE + threadIdx.x * ST_PER;
+    __shared__ uint64_t sw[SD_WAVES];
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
     uint64_t s = 0ull, dead = 0ull;
     int bad = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < ST_PER; k++) {
+    for (uint32_t k = 0; k < SD_PER; k++) {
         const uint64_t i = first + k;
         if (i >= a.count) break;
         const uint64_t size = a.val_size[i];
@@ -499,8 +470,8 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_compact_reduce_kernel(LzfCompact
         }
     }
     uint64_t tot, dtot;
-    (void)dv_block_excl<ST_WAVES>(s, sw, &tot);
-    (void)dv_block_excl<ST_WAVES>(dead, sw, &dtot);
+    (void)dv_block_excl<SD_WAVES>(s, sw, &tot);
+    (void)dv_block_excl<SD_WAVES>(dead, sw, &dtot);
     if (RANGE) bad = __syncthreads_or(bad);
     if (threadIdx.x != 0u) return;
     a.w_tile_n[blockIdx.x] = (tot >> 48) | (bad ? ST_TILE_BAD : 0ull);
@@ -512,20 +483,20 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_compact_reduce_kernel(LzfCompact
  * of the tiles' live counts and live bytes in place and the whole-call
  * decision */
 template <bool COMPACT>
-__global__ __launch_bounds__(ST_BLOCK) void lzf_compact_carry_kernel(LzfCompactArgs a, uint32_t ntile)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_compact_carry_kernel(LzfCompactArgs a, uint32_t ntile)
 {
-    __shared__ uint64_t sw[ST_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     uint64_t rn = 0ull, rb = 0ull, rd = 0ull;
     int bad = 0;
-    for (uint32_t c = 0; c < ntile; c += ST_BLOCK) {
+    for (uint32_t c = 0; c < ntile; c += SD_BLOCK) {
         const uint32_t i = c + threadIdx.x;
         uint64_t xn = i < ntile ? a.w_tile_n[i] : 0ull;
         const uint64_t xb = i < ntile ? a.w_tile_b[i] : 0ull, xd = i < ntile ? a.w_tile_d[i] : 0ull;
         bad |= (int)(xn >> 63);
         xn &= ~ST_TILE_BAD;
         uint64_t tn, tb, td;
-        const uint64_t on = dv_block_excl<ST_WAVES>(xn, sw, &tn), ob = dv_block_excl<ST_WAVES>(xb, sw, &tb);
-        (void)dv_block_excl<ST_WAVES>(xd, sw, &td);
+        const uint64_t on = dv_block_excl<SD_WAVES>(xn, sw, &tn), ob = dv_block_excl<SD_WAVES>(xb, sw, &tb);
+        (void)dv_block_excl<SD_WAVES>(xd, sw, &td);
         if (COMPACT && i < ntile) {
             a.w_tile_n[i] = rn + on;
             a.w_tile_b[i] = rb + ob;
@@ -556,24 +527,24 @@ __global__ __launch_bounds__(ST_BLOCK) void lzf_compact_carry_kernel(LzfCompactA
 /* an accepted call only: the live list, then every item's new offset and a
  * dead item's size 0.  An item's old offset is read by the thread that
  * replaces it, and the pack kernel reads the list, not val_off */
-__global__ __launch_bounds__(ST_BLOCK) void lzf_compact_write_kernel(LzfCompactArgs a)
+__global__ __launch_bounds__(SD_BLOCK) void lzf_compact_write_kernel(LzfCompactArgs a)
 {
-    __shared__ uint64_t sw[ST_WAVES];
+    __shared__ uint64_t sw[SD_WAVES];
     if (a.w_state[ST_STATUS] != 0ull) return;             /* refused: the arrays stay as they are */
-    const uint64_t first = (uint64_t)blockIdx.x * ST_TILE + threadIdx.x * ST_PER;
-    uint64_t v[ST_PER], s = 0ull;
+    const uint64_t first = (uint64_t)blockIdx.x * SD_TILE + threadIdx.x * SD_PER;
+    uint64_t v[SD_PER], s = 0ull;
 #pragma unroll
-    for (uint32_t k = 0; k < ST_PER; k++) {
+    for (uint32_t k = 0; k < SD_PER; k++) {
         const uint64_t i = first + k;
         v[k] = i < a.count && a.enc[i] != (uint8_t)LZF_ENC_NULL ? ST_LIVE_ONE + a.val_size[i] : 0ull;
         s += v[k];
     }
     uint64_t tot;
-    const uint64_t o = dv_block_excl<ST_WAVES>(s, sw, &tot);
+    const uint64_t o = dv_block_excl<SD_WAVES>(s, sw, &tot);
     uint64_t rank = a.w_tile_n[blockIdx.x] + (o >> 48);
     uint64_t off = a.w_state[ST_BASE] + a.w_tile_b[blockIdx.x] + (o & ST_LIVE_BYTES);
 #pragma unroll
-    for (uint32_t k = 0; k < ST_PER; k++) {
+    for (uint32_t k = 0; k < SD_PER; k++) {
         const uint64_t i = first + k;
         if (i >= a.count) break;
         if (v[k]) {
@@ -602,48 +573,37 @@ struct StPackLive {
     __device__ inline uint64_t total() const { return a.w_state[ST_TOTAL]; }
 };
 
-#define ST_SWEEP_GRID 2048u               /* grid-stride kernels: 256 CUs x 8 workgroups */
-
 /* DEL / overwrite by index.  Byte stores: indices that share a 4-byte word of
  * enc, or repeat, all store the same byte and none reads */
-__global__ __launch_bounds__(ST_BLOCK) void lzf_store_delete_kernel(const uint32_t *__restrict__ idx, uint32_t n,
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_delete_kernel(const uint32_t *__restrict__ idx, uint32_t n,
                                                                     uint8_t *enc, uint32_t count)
 {
-    const uint64_t step = (uint64_t)gridDim.x * ST_BLOCK;
-    for (uint64_t k = (uint64_t)blockIdx.x * ST_BLOCK + threadIdx.x; k < n; k += step) {
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
+    for (uint64_t k = (uint64_t)blockIdx.x * SD_BLOCK + threadIdx.x; k < n; k += step) {
         const uint32_t i = idx[k];
         if (i < count) enc[i] = (uint8_t)LZF_ENC_NULL;
     }
 }
 
-/* the TTL rule of src/query.c:186-189 over every item that is not NULL yet;
- * the count by wave ballot, one atomic add per wave.  Every lane of a
- * workgroup makes the same number of rounds */
-__global__ __launch_bounds__(ST_BLOCK) void lzf_store_expire_kernel(const int64_t *__restrict__ item_time,
-                                                                    const int32_t *__restrict__ ttl, int64_t now,
-                                                                    uint8_t *enc, uint32_t count, uint32_t *expired)
+/* the TTL rule (mg_ttl_reached) over every item that is not NULL yet; the
+ * count by wave ballot, one atomic add per wave.  Every lane of a workgroup
+ * makes the same number of rounds */
+__global__ __launch_bounds__(SD_BLOCK) void lzf_store_expire_kernel(LzfItems it, uint32_t *expired)
 {
-    const uint64_t step = (uint64_t)gridDim.x * ST_BLOCK;
+    const int64_t *__restrict__ item_time = it.item_time;
+    const int32_t *__restrict__ ttl = it.item_ttl;
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
     uint32_t hits = 0u;
-    for (uint64_t b = (uint64_t)blockIdx.x * ST_BLOCK; b < count; b += step) {
+    for (uint64_t b = (uint64_t)blockIdx.x * SD_BLOCK; b < it.count; b += step) {
         const uint64_t i = b + threadIdx.x;
         bool hit = false;
-        if (i < count && enc[i] != (uint8_t)LZF_ENC_NULL) {
-            const int32_t t = ttl[i];
-            /* now - time in two's complement, as the reference's time_t arithmetic wraps */
-            const int64_t age = (int64_t)((uint64_t)now - (uint64_t)item_time[i]);
-            hit = t > 0 && age >= (int64_t)t;
-            if (hit) enc[i] = (uint8_t)LZF_ENC_NULL;
+        if (i < it.count && it.enc[i] != (uint8_t)LZF_ENC_NULL) {
+            hit = mg_ttl_reached(ttl[i], it.now, item_time, i);
+            if (hit) it.enc[i] = (uint8_t)LZF_ENC_NULL;
         }
-        hits += (uint32_t)__popcll(__ballot(hit));
+        hits += sd_count(hit);
     }
-    if ((threadIdx.x & 63u) == 0u && hits) atomicAdd(expired, hits);
-}
-
-static inline uint32_t st_sweep_grid(uint64_t n)
-{
-    const uint64_t g = (n + ST_BLOCK - 1u) / ST_BLOCK;
-    return (uint32_t)(g < ST_SWEEP_GRID ? g : ST_SWEEP_GRID);
+    sd_leader_add(expired, hits);
 }
 
 /* LZF_GPU_STORE_TILE_KB (diagnostics, read per launch): the pack tile in KiB,
@@ -675,42 +635,20 @@ hipError_t st_launch_pack(const P &p, uint64_t most_bytes, hipStream_t s)
     const uint64_t most = most_bytes / tile + 2u;
     const uint32_t grid = (uint32_t)(most < ST_PACK_GRID ? most : ST_PACK_GRID);
     if (st_pack_realign())
-        hipLaunchKernelGGL((lzf_store_pack_kernel<true, P>), dim3(grid), dim3(ST_BLOCK), 0, s, p, tile);
+        hipLaunchKernelGGL((lzf_store_pack_kernel<true, P>), dim3(grid), dim3(SD_BLOCK), 0, s, p, tile);
     else
-        hipLaunchKernelGGL((lzf_store_pack_kernel<false, P>), dim3(grid), dim3(ST_BLOCK), 0, s, p, tile);
+        hipLaunchKernelGGL((lzf_store_pack_kernel<false, P>), dim3(grid), dim3(SD_BLOCK), 0, s, p, tile);
     return hipGetLastError();
 }
 
 }  // namespace
 
-uint64_t lzf_store_work_bytes(uint32_t count, uint64_t in_bytes)
-{
-    /* state (8 x u64) | slot_off (u64) | tile sums (u64 per tile) | len, cap,
-     * out_len (u32) | the slots, and 16 bytes the realigning loads may read
-     * past them; room to align the caller's pointer */
-    const uint64_t fixed = 64u + (uint64_t)count * (8u + 3u * 4u) + (uint64_t)st_tiles(count) * 8u + 16u + 16u;
-    const uint64_t room = st_slot_room(in_bytes, count);
-    return room > ~0ull - fixed ? ~0ull : room + fixed;
-}
-
-void lzf_store_carve(LzfStoreArgs &a, void *work)
-{
-    uint8_t *w = (uint8_t *)(((uintptr_t)work + 15u) & ~(uintptr_t)15u);
-    a.w_state = (uint64_t *)w;            w += 64;
-    a.w_slot_off = (uint64_t *)w;         w += (size_t)a.count * 8;
-    a.w_tile = (uint64_t *)w;             w += (size_t)st_tiles(a.count) * 8;
-    a.w_len = (uint32_t *)w;              w += (size_t)a.count * 4;
-    a.w_cap = (uint32_t *)w;              w += (size_t)a.count * 4;
-    a.w_out = (uint32_t *)w;              w += (size_t)a.count * 4;
-    a.w_slots = w;
-}
-
 hipError_t lzf_launch_store(LzfStoreArgs &a, hipStream_t s, hipError_t (*compress)(const LzfBatch &, hipStream_t))
 {
-    const uint32_t nt = st_tiles(a.count);
-    hipLaunchKernelGGL(lzf_store_reduce_kernel<false>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(lzf_store_carry_kernel<false>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
-    hipLaunchKernelGGL(lzf_store_write_kernel<false>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    const uint32_t nt = sd_tiles(a.count);
+    hipLaunchKernelGGL(lzf_store_reduce_kernel<false>, dim3(nt), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_store_carry_kernel<false>, dim3(1), dim3(SD_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_store_write_kernel<false>, dim3(nt), dim3(SD_BLOCK), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     /* a batch with no candidate at all (max_in_len 0) is not compressed */
@@ -719,62 +657,41 @@ hipError_t lzf_launch_store(LzfStoreArgs &a, hipStream_t s, hipError_t (*compres
         LzfBatch b{a.in, a.in_off, a.w_len, a.w_slots, a.w_slot_off, a.w_cap, a.w_out, nullptr, a.count, a.max_in_len};
         if ((e = compress(b, s)) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(lzf_store_reduce_kernel<true>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(lzf_store_carry_kernel<true>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
-    hipLaunchKernelGGL(lzf_store_write_kernel<true>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_store_reduce_kernel<true>, dim3(nt), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_store_carry_kernel<true>, dim3(1), dim3(SD_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_store_write_kernel<true>, dim3(nt), dim3(SD_BLOCK), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    return st_launch_pack(StPackSet{a}, st_slot_room(a.in_bytes, a.count), s);
-}
-
-uint64_t lzf_compact_work_bytes(uint32_t count)
-{
-    /* state (8 x u64) | three tile sums (u64 per tile) | the live list (2 x
-     * u64 per item); room to align the caller's pointer.  Below 2^37 */
-    return 64u + (uint64_t)st_tiles(count) * 24u + (uint64_t)count * 16u + 16u;
-}
-
-void lzf_compact_carve(LzfCompactArgs &a, void *work)
-{
-    uint8_t *w = (uint8_t *)(((uintptr_t)work + 15u) & ~(uintptr_t)15u);
-    const size_t nt = st_tiles(a.count);
-    a.w_state = (uint64_t *)w;            w += 64;
-    a.w_tile_n = (uint64_t *)w;           w += nt * 8;
-    a.w_tile_b = (uint64_t *)w;           w += nt * 8;
-    a.w_tile_d = (uint64_t *)w;           w += nt * 8;
-    a.w_live_dst = (uint64_t *)w;         w += (size_t)a.count * 8;
-    a.w_live_src = (uint64_t *)w;
+    return st_launch_pack(StPackSet{a}, sd_slot_room(a.in_bytes, a.count), s);
 }
 
 hipError_t lzf_launch_store_delete(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count, hipStream_t s)
 {
-    hipLaunchKernelGGL(lzf_store_delete_kernel, dim3(st_sweep_grid(n)), dim3(ST_BLOCK), 0, s, idx, n, enc, count);
+    hipLaunchKernelGGL(lzf_store_delete_kernel, dim3(sd_sweep_grid(n)), dim3(SD_BLOCK), 0, s, idx, n, enc, count);
     return hipGetLastError();
 }
 
-hipError_t lzf_launch_store_expire(const int64_t *item_time, const int32_t *ttl, int64_t now, uint8_t *enc,
-                                   uint32_t count, uint32_t *expired, hipStream_t s)
+hipError_t lzf_launch_store_expire(const LzfItems &it, uint32_t *expired, hipStream_t s)
 {
     const hipError_t e = hipMemsetAsync(expired, 0, sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lzf_store_expire_kernel, dim3(st_sweep_grid(count)), dim3(ST_BLOCK), 0, s, item_time, ttl, now,
-                       enc, count, expired);
+    hipLaunchKernelGGL(lzf_store_expire_kernel, dim3(sd_sweep_grid(it.count)), dim3(SD_BLOCK), 0, s, it, expired);
     return hipGetLastError();
 }
 
 hipError_t lzf_launch_store_usage(LzfCompactArgs &a, hipStream_t s)
 {
-    const uint32_t nt = st_tiles(a.count);
-    hipLaunchKernelGGL(lzf_compact_reduce_kernel<false>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(lzf_compact_carry_kernel<false>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
+    const uint32_t nt = sd_tiles(a.count);
+    hipLaunchKernelGGL(lzf_compact_reduce_kernel<false>, dim3(nt), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_compact_carry_kernel<false>, dim3(1), dim3(SD_BLOCK), 0, s, a, nt);
     return hipGetLastError();
 }
 
 hipError_t lzf_launch_store_compact(LzfCompactArgs &a, hipStream_t s)
 {
-    const uint32_t nt = st_tiles(a.count);
-    hipLaunchKernelGGL(lzf_compact_reduce_kernel<true>, dim3(nt), dim3(ST_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(lzf_compact_carry_kernel<true>, dim3(1), dim3(ST_BLOCK), 0, s, a, nt);
-    hipLaunchKernelGGL(lzf_compact_write_kernel, dim3(nt), dim3(ST_BLOCK), 0, s, a);
+    const uint32_t nt = sd_tiles(a.count);
+    hipLaunchKernelGGL(lzf_compact_reduce_kernel<true>, dim3(nt), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_compact_carry_kernel<true>, dim3(1), dim3(SD_BLOCK), 0, s, a, nt);
+    hipLaunchKernelGGL(lzf_compact_write_kernel, dim3(nt), dim3(SD_BLOCK), 0, s, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     /* the live bytes fit in both arenas, or the call is refused */

@@ -622,6 +622,46 @@ def test_select_past_the_carry_chunk(torch):
     assert (got[:len(exp)] == exp).all() and (got[len(exp):cap] == PAD).all() and (got[cap:] == 0x5A5A5A5A).all()
 
 
+@pytest.mark.gpu
+def test_select_of_a_sparse_store_past_one_piece_of_the_carry_scan(torch):
+    # 2 048 tiles of 1 024 items are one piece of the scan over the tile counts; the carry between
+    # pieces shows only past that.  A store of dead items, with live ones at both ends and around the
+    # seam; a dead item's key matches the prefix too
+    seam = 2048 * 1024
+    count = seam + 1025
+    rnd = random.Random(0x5E1EC7)
+    fixed = [0, 1, 1023, 1024, seam - 1, seam, seam + 1, count - 1]
+    live = set(fixed) | set(rnd.sample(range(2, seam - 1), 150)) | set(rnd.sample(range(seam + 2, count - 1), 150))
+    live = sorted(live)
+    keys = np.tile(np.frombuffer(b"ab:z", np.uint8), count)
+    enc = np.full(count, ENC_NULL, np.uint8)
+    exp = []
+    for i in live:
+        enc[i] = rnd.choice([ENC_PLAIN, ENC_LZF, ENC_NUMBER])
+        if i in fixed or rnd.random() < 2 / 3:
+            exp.append(i)
+        else:
+            keys[4 * i:4 * i + 4] = np.frombuffer(b"a:bz", np.uint8)
+    assert len(live) > 300 and len(exp) < len(live) and sum(1 for i in exp if i >= seam) > 50
+    d_keys = _u8(torch, np.concatenate([np.zeros(3, np.uint8), keys, np.zeros(8, np.uint8)]))
+    d_koff = _i64(torch, np.arange(count, dtype=np.int64) * 4 + 3)
+    d_klen, d_enc = _i32(torch, np.full(count, 4, np.uint32)), _u8(torch, enc)
+    d_prefix = _u8(torch, np.frombuffer(b"ab:", np.uint8))
+    wsize = int(gibson_amd.lib().lzf_gpu_store_select_work_size(count))
+    for cap in (len(exp) + 9, len(exp) // 2):
+        sel = torch.full((cap + 16,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+        res = torch.full((2,), -1, dtype=torch.int32, device="cuda")
+        work = torch.full((wsize + ROOM,), GUARD, dtype=torch.uint8, device="cuda")
+        gibson_amd.store_select_prefix(d_keys, d_koff, d_klen, d_enc, d_prefix, sel[:cap], res, work=work[:wsize])
+        torch.cuda.synchronize()
+        got = sel.cpu().numpy().view(np.uint32)
+        k = min(len(exp), cap)
+        assert res.cpu().numpy().tolist() == [k, len(exp)]
+        assert got[:k].tolist() == exp[:k]
+        assert (got[k:cap] == PAD).all() and (got[cap:] == 0x5A5A5A5A).all()
+        assert (work[wsize:].cpu().numpy() == GUARD).all()
+
+
 # 8
 def select_list(torch, d, prefix, cap):
     sel = torch.full((cap,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")

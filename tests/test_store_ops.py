@@ -719,6 +719,57 @@ def test_converted_offsets_follow_the_list_order(torch):
     assert [int(off[i]) for i in conv] == [s0.used + 8 * r for r in range(len(conv))]
 
 
+@pytest.mark.gpu
+def test_list_past_one_piece_of_the_tile_scan(torch):
+    # 2 048 tiles of 1 024 entries are one piece of the scan over the tile counts; the carry between
+    # pieces shows only past that.  Mostly padding, with entries at both ends and around the seam
+    seam = 2048 * 1024
+    n = seam + 1025
+    rnd = random.Random(0x5EA2)
+    where = {0, 1, 1023, 1024, seam - 1, seam, seam + 1, n - 1}
+    where |= set(rnd.sample(range(2, seam - 1), 150)) | set(rnd.sample(range(seam + 2, n - 1), 150))
+    where = np.array(sorted(where))
+    values, encs = [], []
+    for k in range(len(where)):
+        kind = "numeric" if k < 8 else rnd.choice(["numeric"] * 4 + ["number", "text", "dead"])
+        if kind == "numeric":
+            values.append(b"%d" % rnd.randrange(-10**9, 10**9))
+        elif kind == "number":
+            values.append(le64(rnd.randrange(-10**9, 10**9)))
+        else:
+            values.append(b"x%d" % k)
+        encs.append(ENC_NUMBER if kind == "number" else ENC_NULL if kind == "dead" else ENC_PLAIN)
+    s0 = Store(values, encs)
+    items = np.random.RandomState(0x5EA2).permutation(len(where)).astype(np.uint32)   # list order is not item order
+    idx = np.full(n, PAD, np.uint32)
+    idx[where] = items
+    cap = s0.used + 8 * len(where)
+    # the model over the real entries alone: a padding entry is DEAD, its value 0, and counts nowhere
+    s = s0.copy()
+    status, res, st, val = model_minc(s, items, 5, False, NOW, cap)
+    assert status == OK and {DONE, CONVERTED, NAN, DEAD} <= set(st)
+    conv = [k for k in range(len(where)) if st[k] == CONVERTED]
+    assert sum(1 for k in conv if where[k] >= seam) > 50           # ranks that need the carry
+    exp_st = np.full(n, DEAD, np.uint8)
+    exp_st[where] = st
+    exp_val = np.zeros(n, np.int64)
+    exp_val[where] = val
+    d, o = Dev(torch, s0, cap), Out(torch, n, 6)
+    gibson_amd.store_minc(_i32(torch, idx), 5, d.a("arena"), d.used[:1], d.a("off"), d.a("size"), d.a("enc"),
+                          d.a("time"), d.a("ttl"), d.a("lock"), NOW, o.result[:6], o.status[:1],
+                          last_access=d.a("last"), entry_status=o.est[:n], entry_value=o.ev[:n], work=o.work[:o.wsize])
+    d.check(s)                                                     # values, descriptors, *store_used, the guards
+    off = d.off.cpu().numpy()
+    assert [int(off[items[k]]) for k in conv] == [s0.used + 8 * r for r in range(len(conv))]
+    assert int(d.used[0].item()) == s0.used + 8 * len(conv)
+    assert o.result.cpu().numpy().tolist() == res + [UNSET] * 4
+    assert o.status.cpu().numpy().tolist() == [OK] + [UNSET] * 4
+    est, ev = o.est.cpu().numpy(), o.ev.cpu().numpy()
+    assert (est[:n] == exp_st).all() and (est[n:] == 0x77).all()
+    assert (ev[:n] == exp_val).all() and (ev[n:] == UNSET).all()
+    assert (o.work[o.wsize:].cpu().numpy() == GUARD).all()
+
+
 # 7
 @pytest.mark.gpu
 def test_full_boundary(torch, mixed):
