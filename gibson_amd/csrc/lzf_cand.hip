@@ -44,14 +44,8 @@
 #include "lzf_dev.h"
 
 /* record of position p: bits 0-12 off1 = p - q1 - 1, 13-15 code1,
- * bits 16-28 off2 = p - q2 - 1, 29-31 code2.  Codes:
- *   0     none (no earlier position with p's slot inside p's window, or only
- *         position 0, which is never a ref: src/lzf_c.c:155 `ref > in_data`)
- *   1     same slot, the three bytes differ (slot collision)
- *   2..6  the bytes agree for exactly code + 1 bytes (3..7)
- *   7     the bytes agree for >= 8 bytes                                   */
-#define RC_DIFF 1u
-#define RC_LONG 7u
+ * bits 16-28 off2 = p - q2 - 1, 29-31 code2; the codes are dv_code's
+ * (lzf_dev.h) */
 
 #ifndef KT_WIN
 #define KT_WIN 15u                /* windows of 64 positions per block = worker waves: 15 + the table wave = 4 per SIMD */
@@ -65,45 +59,21 @@
 #define KT_CL 2u                /* steps from C1 (agreement loads issued) to C2 (consumed); divides KT_PF */
 #endif
 
-/* v_ffbl_b32: the lowest set bit's index, 0xFFFFFFFF for 0 (defined here,
- * unlike __builtin_ctz) */
-__device__ __forceinline__ uint32_t kt_ffbl(uint32_t x)
-{
-    uint32_t r;
-    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-__device__ __forceinline__ uint32_t kt_code(uint32_t k)
-{
-    return k < 3u ? RC_DIFF : (k >= 8u ? RC_LONG : k - 1u);
-}
-
-
 static_assert(KT_WIN % 5u == 0u, "the exchanges go in groups of 5 windows");
-/* LDS byte address of a __shared__ object */
-__device__ __forceinline__ uint32_t kt_lds_addr(const void *p)
-{
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
 /* five windows' exchanges, issued in window (= position) order, then one
  * wait: the LDS writes the results after issue, so they are outputs of the
  * same asm statement (early-clobber: no result shares an input's register)
  * and nothing reads them before the wait.  Groups of five keep the table
- * wave's live registers inside the workers' budget (15 at once spills) */
-#define KT_X(i_) "ds_mskor_rtn_b32 %" #i_ ", %[a" #i_ "], %[m" #i_ "], %[d" #i_ "]\n\t"
-#define KT_IN(i_) [a##i_] "v"(a[i_]), [m##i_] "v"(m[i_]), [d##i_] "v"(d[i_])
+ * wave's live registers inside the workers' budget (dv_xchg15's 15 at once
+ * spill here); the operand macros are lzf_dev.h's */
 __device__ __forceinline__ void kt_xchg5(uint32_t (&r)[5], const uint32_t (&a)[5], const uint32_t (&m)[5],
                                          const uint32_t (&d)[5])
 {
-    asm volatile(KT_X(0) KT_X(1) KT_X(2) KT_X(3) KT_X(4) "s_waitcnt lgkmcnt(0)"
+    asm volatile(DV_MSKOR(0) DV_MSKOR(1) DV_MSKOR(2) DV_MSKOR(3) DV_MSKOR(4) "s_waitcnt lgkmcnt(0)"
                  : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4])
-                 : KT_IN(0), KT_IN(1), KT_IN(2), KT_IN(3), KT_IN(4)
+                 : DV_MSKOR_IN(0, 0), DV_MSKOR_IN(1, 0), DV_MSKOR_IN(2, 0), DV_MSKOR_IN(3, 0), DV_MSKOR_IN(4, 0)
                  : "memory");
 }
-#undef KT_X
-#undef KT_IN
-/* S entry of a position of the block: its slot and whether it is active */
-#define KS_ACT  (1u << 16)
 
 /* the 8 bytes at pp: one branch-free 8-byte load for values of >= 8 bytes
  * (the compiler then counts the loads in flight instead of draining them) */
@@ -180,23 +150,6 @@ struct KtLds {
 };
 
 template <uint32_t V> struct KtIc { static constexpr uint32_t value = V; };
-/* KT_INTERIOR (round 5): the main loop's steps with their block and position
- * tests dropped (they hold there); the first KT_PF steps keep them */
-#ifndef KT_INTERIOR
-#define KT_INTERIOR 1
-#endif
-/* KT_SPRE (round 5): workers store the table wave's exchange address */
-#ifndef KT_SPRE
-#define KT_SPRE 1
-#endif
-/* round 5: C2's agreements without 64-bit compares, C1's q2 index by selects */
-#ifndef KT_AGREE2
-#define KT_AGREE2 1
-#endif
-#ifndef KT_IQSEL
-#define KT_IQSEL 1
-#endif
-
 #ifdef KT_TIMING
 #define KT_ACC_ARG , uint64_t *kt_acc, uint32_t *kt_busy
 #define KT_ACC_PASS , kt_acc, kt_busy
@@ -209,16 +162,8 @@ __device__ __forceinline__ void kt_value(const KtLds &L, const uint8_t *src, uin
 {
     uint16_t *const T = L.T, *const Q = L.Q, *const O = L.O;
     uint32_t *const S = L.S;
-#ifdef KT_WREV
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, w = KT_WIN - (tid >> 6);   /* experiment: table wave last */
-#else
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-#endif
-#ifdef KT_JREV
-    const uint32_t j = KT_WIN - w;                             /* experiment: windows in reverse wave order */
-#else
     const uint32_t j = w - 1u;                                 /* worker's window (w >= 1) */
-#endif
     const uint32_t np = n - 2u;                                /* positions 0 .. n-3, src/lzf_c.c:145 */
     const uint32_t nb = (np + KT_BLK - 1u) / KT_BLK;
     /* worker: the 8 bytes of its position in the next KT_PF blocks are in
@@ -266,7 +211,7 @@ __device__ __forceinline__ void kt_value(const KtLds &L, const uint8_t *src, uin
         /* CLAMP: the step's loads may reach past the value (its last
          * blocks); otherwise they are plain 8-byte loads */
         constexpr bool CLAMP = SMALL || decltype(clamp)::value == 1u;
-        /* INTERIOR (clamp 2, KT_INTERIOR): t >= KT_PF and blocks t-3 .. t +
+        /* INTERIOR (clamp 2): t >= KT_PF and blocks t-3 .. t +
          * KT_PF + 3 lie inside the value, so every block and position test
          * of the step holds; they are dropped (no exec-mask branches) */
         constexpr bool INTERIOR = !SMALL && decltype(clamp)::value == 2u;
@@ -290,9 +235,6 @@ __device__ __forceinline__ void kt_value(const KtLds &L, const uint8_t *src, uin
                 const uint32_t k = t - 1u, B = KT_BLK * k;
                 const uint32_t *Sk = S + KT_BLK * (k & 1u);
                 uint16_t *Ok = O + KT_BLK * m3_1;
-                /* a position past the value exchanges in its lane's own
-                 * dummy half (T[65536 + lane]) */
-                const uint32_t tb = kt_lds_addr(T);
 #pragma unroll
                 for (uint32_t g = 0; g < KT_WIN; g += 5u) {
                     uint32_t xa[5], xm[5], xd[5], xr[5], xs[5];
@@ -300,17 +242,11 @@ __device__ __forceinline__ void kt_value(const KtLds &L, const uint8_t *src, uin
                     for (uint32_t u = 0; u < 5u; u++) {
                         const uint32_t i = g + u;
                         const uint32_t e = Sk[64u * i + lane];
-#if KT_SPRE
-                        /* the worker stored the exchange's dword address and
-                         * the slot's half (bit 0) */
-                        (void)tb;
+                        /* the worker stored the exchange's dword address and the
+                         * slot's half (bit 0); a position past the value exchanges
+                         * in its lane's own dummy half (T[65536 + lane]) */
                         xs[u] = (e & 1u) << 4;
                         xa[u] = e & ~3u;
-#else
-                        const uint32_t h = (e & KS_ACT) ? (e & 0xFFFFu) : LZF_SLOTS + lane;
-                        xs[u] = (h & 1u) << 4;
-                        xa[u] = tb + 4u * (h >> 1);
-#endif
                         xm[u] = 0xFFFFu << xs[u];
                         xd[u] = (((B + 64u * i) & 0xFFFFu) | lane) << xs[u];   /* B + 64 i: a multiple of 64 */
                     }
@@ -327,18 +263,13 @@ __device__ __forceinline__ void kt_value(const KtLds &L, const uint8_t *src, uin
                 /* branch-free: both agreements always, the record by selects */
                 const uint64_t x1 = ((uint64_t)(ca.y ^ cb1.y) << 32) | (uint64_t)(ca.x ^ cb1.x);
                 const uint64_t x2 = ((uint64_t)(ca.y ^ cb2.y) << 32) | (uint64_t)(ca.x ^ cb2.x);
-#if KT_AGREE2
                 /* first differing byte of 8 (8: none), without the 64-bit compare
                  * and select: v_ffbl gives the lowest set bit or ~0 for none, so
                  * min3(ffbl(lo), ffbl(hi) | 32, 64) is the first differing bit */
-                const uint32_t k1 = min(min(min(kt_ffbl((uint32_t)x1), kt_ffbl((uint32_t)(x1 >> 32)) | 32u), 64u) >> 3, cav);
-                const uint32_t k2 = min(min(min(kt_ffbl((uint32_t)x2), kt_ffbl((uint32_t)(x2 >> 32)) | 32u), 64u) >> 3, cav);
-#else
-                const uint32_t k1 = min(x1 ? (uint32_t)__builtin_ctzll(x1) >> 3 : 8u, cav);
-                const uint32_t k2 = min(x2 ? (uint32_t)__builtin_ctzll(x2) >> 3 : 8u, cav);
-#endif
-                const uint32_t r1 = (cp - cq1 - 1u) | (kt_code(k1) << 13);
-                const uint32_t r2 = ((cp - cq2 - 1u) | (kt_code(k2) << 13)) << 16;
+                const uint32_t k1 = min(min(min(dv_ffbl((uint32_t)x1), dv_ffbl((uint32_t)(x1 >> 32)) | 32u), 64u) >> 3, cav);
+                const uint32_t k2 = min(min(min(dv_ffbl((uint32_t)x2), dv_ffbl((uint32_t)(x2 >> 32)) | 32u), 64u) >> 3, cav);
+                const uint32_t r1 = (cp - cq1 - 1u) | (dv_code(k1) << 13);
+                const uint32_t r2 = ((cp - cq2 - 1u) | (dv_code(k2) << 13)) << 16;
                 rec[cp] = cq1 ? (r1 | (cq2 ? r2 : 0u)) : 0u;
             }
             /* ---- Q <- O of block t-3 ---------------------------------------- */
@@ -361,17 +292,11 @@ __device__ __forceinline__ void kt_value(const KtLds &L, const uint8_t *src, uin
                 const uint32_t q1r = Ok[64u * j + lane];
                 const uint32_t q1 = act && p - q1r <= LZF_WINDOW ? q1r : 0u;   /* q1r = 0: none */
                 const uint32_t ik = LZF_WINDOW + KT_BLK * m3_2, ip = LZF_WINDOW + KT_BLK * m3;   /* (k + 2) % 3 = t % 3 */
-#if KT_IQSEL
                 /* all three indices, then selects (the nested ternary compiled to
                  * exec-mask branches: ~20 SALU per step) */
                 const uint32_t iq0 = ik + (q1 - B), iq1 = ip + (q1 + KT_BLK - B), iq2 = q1 & (LZF_WINDOW - 1u);
                 const uint32_t iq01 = q1 + KT_BLK >= B ? iq1 : iq2;
                 const uint32_t iq = q1 >= B ? iq0 : iq01;
-#else
-                const uint32_t iq = q1 >= B ? ik + (q1 - B)
-                                  : q1 + KT_BLK >= B ? ip + (q1 + KT_BLK - B)
-                                                     : (q1 & (LZF_WINDOW - 1u));
-#endif
                 const uint32_t q2r = Q[iq];
                 const uint32_t q2 = q1 && q2r != 0u && p - q2r <= LZF_WINDOW ? q2r : 0u;
                 c_p[CS] = act ? p : 0xFFFFFFFFu;
@@ -388,18 +313,14 @@ __device__ __forceinline__ void kt_value(const KtLds &L, const uint8_t *src, uin
                 const uint2 a = pf[PS];
                 ak[PS] = a;
                 const uint32_t s = dv_slot(a.x);
-#if KT_SPRE
                 {
                     /* the table wave's exchange address (T's dword of the slot,
                      * or the lane's dummy past the value) and half, so it does
                      * not compute them: it shares its SIMD with three workers
                      * and sets the step's pace there (tools/kt_trace.py) */
                     const uint32_t h = act ? s : LZF_SLOTS + lane;
-                    S[KT_BLK * (t & 1u) + 64u * j + lane] = kt_lds_addr(T) + 4u * (h >> 1) + (h & 1u);
+                    S[KT_BLK * (t & 1u) + 64u * j + lane] = dv_lds_addr(T) + 4u * (h >> 1) + (h & 1u);
                 }
-#else
-                S[KT_BLK * (t & 1u) + 64u * j + lane] = act ? (s | KS_ACT) : 0u;
-#endif
             }
         }
         if (w) KT_TM(4);
@@ -444,7 +365,7 @@ __device__ __forceinline__ void kt_value(const KtLds &L, const uint8_t *src, uin
     uint32_t t = 0, m3 = 0;                                    /* m3 = t % 3 */
     const auto next3 = [](uint32_t x) { return x == 2u ? 0u : x + 1u; };
     if (!SMALL) {
-        if (KT_INTERIOR && KT_BLK * (KT_PF + 3u + KT_PF + 1u) + 8u <= n) {
+        if (KT_BLK * (KT_PF + 3u + KT_PF + 1u) + 8u <= n) {
             /* the first KT_PF steps test their blocks (t - 3 < 0 ...) */
             step(KtIc<0>{}, KtIc<0>{}, 0u, 0u);
             step(KtIc<1>{}, KtIc<0>{}, 1u, 1u);
@@ -501,18 +422,6 @@ __global__ __launch_bounds__(KT_THREADS) void lzf_cand_table_kernel(LzfBatch bt,
     uint16_t *const Q = QO, *const O = QO + LZF_WINDOW;
     __shared__ uint32_t S[2u * KT_BLK];
     const KtLds L{T, Q, O, S};
-#ifdef KT_PMAP
-    {
-        /* per-wave issue priority, 2 bits per wave index (experiment) */
-        const uint32_t pw = (uint32_t)((KT_PMAP >> (4u * (threadIdx.x >> 6))) & 3u);
-        if (pw == 1u) __builtin_amdgcn_s_setprio(1);
-        else if (pw == 2u) __builtin_amdgcn_s_setprio(2);
-        else if (pw == 3u) __builtin_amdgcn_s_setprio(3);
-    }
-#endif
-#ifdef KT_PRIO
-    if (threadIdx.x < 64u) __builtin_amdgcn_s_setprio(KT_PRIO);   /* the table wave */
-#endif
 #ifdef KT_TIMING
     /* summed per wave over its values, added once at the end (per-value
      * atomics on one line serialised and skewed the timings) */
@@ -556,33 +465,12 @@ __global__ __launch_bounds__(KT_THREADS) void lzf_cand_table_kernel(LzfBatch bt,
 #define K3_LITX    3u           /* free literals taken after a literal in the same iteration (0: none) */
 #endif
 
-/* rel codes of the walk, relative to p: the record codes 0..7, plus
- * 8 (the first 3 bytes agree, length unknown) and 9 (unknown).
- * K3_EXACT (round 5): exact agreements combine too.  If p~q agree in exactly
- * a bytes and q~r in exactly b != a, then p~r agree in exactly min(a, b) (the
- * first mismatch of the shorter one is a mismatch of p~r, the bytes before
- * it agree in all three); with one of them exact (a < 8) and the other
- * >= 8, exactly the exact one; both >= 8, >= 8.  A deeper candidate's match
- * length then often needs no extension load (a record's agreements are capped
- * at its own remaining bytes, which are more than p's: the cap binds p's
- * first, so the rule holds at the value's end too). */
-#ifndef K3_EXACT
-#define K3_EXACT 1
-#endif
-__device__ __forceinline__ uint32_t k3_comb(uint32_t rel, uint32_t code)
-{
-    /* p~q agree in 3 bytes and q~r agree in 3 bytes => p~r agree in 3;
-     * exactly one of them => p~r differ in the first 3 bytes */
-    if (rel == 9u) return 9u;
-    const bool e1 = rel >= 2u, e2 = code >= 2u;
-    if (!(e1 && e2)) return (e1 != e2) ? RC_DIFF : 9u;
-    if (K3_EXACT && rel <= RC_LONG) {              /* rel exact (2..6) or >= 8 (7); code is 2..7 */
-        if (rel != code) return rel < code ? rel : code;   /* min: an exact one below the other */
-        if (rel == RC_LONG) return RC_LONG;        /* both >= 8 */
-    }
-    return 8u;
-}
-
+/* rel codes of the walk, relative to p: the record codes 0..7, plus 8 (the
+ * first 3 bytes agree, length unknown) and 9 (unknown); links combine by
+ * dv_comb (lzf_dev.h).  This parse takes the exact agreements too (round 5): a
+ * deeper candidate's match length then often needs no extension load
+ * (compress 194.3 -> 187.6 ms on text64k, profiles/r05/INDEX.md). */
+#define K3_EXACT true
 enum { K3_STEP = 0, K3_RESOLVE = 1, K3_DECIDE = 2, K3_EXTEND = 3, K3_EMIT = 4, K3_DONE = 5 };
 
 /* A value shorter than 16 bytes, whole: the reference's loop
@@ -655,6 +543,25 @@ __device__ __noinline__ uint32_t k3_small(const uint8_t *src, uint32_t n, uint8_
 #ifndef K3_MINB
 #define K3_MINB 1
 #endif
+/* the shared output cursor and bitmap ring (lzf_emit.h), with this parse's
+ * ring index (a remainder: K3_RW is any multiple of 4) and input byte: its
+ * window W is one plain 16-byte load, moved back inside the value near its
+ * end (n >= 16) */
+#define EMIT_SITE(i) ((void)0)
+#define EMIT_RW K3_RW
+#define EMIT_THREADS K3_THREADS
+#define EMIT_RING_AT(w_) ((w_) % K3_RW)
+#define EMIT_BYTE(pos_, out_)                                                      \
+    do {                                                                           \
+        uint32_t d_ = (pos_) - wb;                                                 \
+        if (d_ >= 16u) {                                                           \
+            wb = dv_at16(n, (pos_));                                               \
+            W = dv_ld16(src + wb);                                                 \
+            d_ = (pos_) - wb;                                                      \
+        }                                                                          \
+        (out_) = (dv_sel4(W, d_ >> 2) >> (8u * (d_ & 3u))) & 0xFFu;               \
+    } while (0)
+#include "lzf_emit.h"
 __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfBatch bt, LzfRecScratch sc)
 {
     const uint32_t v = blockIdx.x * K3_THREADS + threadIdx.x;
@@ -702,16 +609,7 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
     uint32_t cw = 0u, curw = 0u;       /* inserted-bitmap word of p, in flight */
     __shared__ uint32_t k3_ring[K3_RW][K3_THREADS];
     uint32_t *const ring = &k3_ring[0][threadIdx.x];
-#define K3_RING(w_) ring[((w_) % K3_RW) * K3_THREADS]
-    uint32_t fl = 0u;                  /* bitmap words [0, fl) are in scratch */
-#define K3_FLUSH_TO(w_)                                                            \
-    do {                                                                           \
-        while (fl + K3_RW <= (w_)) {                                               \
-            *(uint4 *)(bits + fl) = make_uint4(K3_RING(fl), K3_RING(fl + 1u),      \
-                                               K3_RING(fl + 2u), K3_RING(fl + 3u)); \
-            fl += 4u;                                                              \
-        }                                                                          \
-    } while (0)
+    uint32_t fl = 0u;                  /* bitmap words [0, fl) are in scratch (EMIT_FLUSH_TO) */
     uint32_t ms = 0u, me = 0u;         /* the last match: [ms, me) */
     uint32_t rel = 0u, q = 0u, k = 0u, lim = 0u, m = 0u;
     uint32_t reln = 0u, qn = 0u;       /* the next chain link from the same record (reln 0: none) */
@@ -726,76 +624,6 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
 #else
 #define K3_CNT(i) ((void)0)
 #endif
-
-/* completed dwords [fs, fw) wait in pb0..2 (slot fw - fs) and leave with
- * the fourth as one 16-byte store; slot and patch selects instead of
- * branches (every branch costs the wave its exec-mask juggling) */
-#define K3_STORE16(w_)                                                             \
-    do {                                                                           \
-        if (fs == 0u && dm != 0u) {        /* dst's first dword: bytes before dst are not ours */ \
-            for (uint32_t t_ = dm; t_ < 4u; t_++) da[t_] = (uint8_t)(pb0 >> (8u * t_)); \
-            const uint2 m_ = make_uint2(pb1, pb2);                                 \
-            __builtin_memcpy(da + 4u, &m_, 8);                                     \
-            const uint32_t l_ = (w_);                                              \
-            __builtin_memcpy(da + 12u, &l_, 4);                                    \
-        } else {                                                                   \
-            const uint4 v_ = make_uint4(pb0, pb1, pb2, (w_));                      \
-            __builtin_memcpy(da + 4u * fs, &v_, 16);                               \
-        }                                                                          \
-    } while (0)
-#define K3_PUT(bytes_, cnt_)                                                       \
-    do {                                                                           \
-        acc |= (uint64_t)(bytes_) << (8u * accn);                                  \
-        accn += (cnt_);                                                            \
-        if (accn >= 4u) {                                                          \
-            const uint32_t w_ = (uint32_t)acc, np_ = fw - fs;                      \
-            pb0 = np_ == 0u ? w_ : pb0;                                            \
-            pb1 = np_ == 1u ? w_ : pb1;                                            \
-            pb2 = np_ == 2u ? w_ : pb2;                                            \
-            if (np_ == 3u) {                                                       \
-                K3_STORE16(w_);                                                    \
-                fs = fw + 1u;                                                      \
-            }                                                                      \
-            fw++;                                                                  \
-            acc >>= 32;                                                            \
-            accn -= 4u;                                                            \
-        }                                                                          \
-    } while (0)
-#define K3_PATCH(x_, byte_)                                                        \
-    do {                                                                           \
-        if ((x_) >= 4u * fw) {                                                     \
-            const uint32_t sh_ = 8u * ((x_) - 4u * fw);                            \
-            acc = (acc & ~(0xFFull << sh_)) | ((uint64_t)(byte_) << sh_);          \
-        } else if ((x_) >= 4u * fs) {                                              \
-            const uint32_t i_ = ((x_) >> 2) - fs, sh_ = 8u * ((x_) & 3u);          \
-            const uint32_t mk_ = ~(0xFFu << sh_), b_ = (uint32_t)(byte_) << sh_;  \
-            pb0 = i_ == 0u ? (pb0 & mk_) | b_ : pb0;                               \
-            pb1 = i_ == 1u ? (pb1 & mk_) | b_ : pb1;                               \
-            pb2 = i_ == 2u ? (pb2 & mk_) | b_ : pb2;                               \
-        } else {                                                                   \
-            da[(x_)] = (uint8_t)(byte_);                                           \
-        }                                                                          \
-    } while (0)
-#define K3_BYTE(pos_, out_)                                                        \
-    do {                                                                           \
-        uint32_t d_ = (pos_) - wb;                                                 \
-        if (d_ >= 16u) {                   /* 16 bytes inside the value (n >= 16) */ \
-            wb = dv_at16(n, (pos_));                                               \
-            W = dv_ld16(src + wb);                                                 \
-            d_ = (pos_) - wb;                                                      \
-        }                                                                          \
-        (out_) = (dv_sel4(W, d_ >> 2) >> (8u * (d_ & 3u))) & 0xFFu;               \
-    } while (0)
-#define K3_LITERAL(pos_)                                                           \
-    do {                                                                           \
-        uint32_t byte_;                                                            \
-        K3_BYTE(pos_, byte_);                                                      \
-        const bool first_ = run == 0u;             /* the run's header slot first */ \
-        hx = first_ ? 4u * fw + accn : hx;                                         \
-        K3_PUT(first_ ? byte_ << 8 : byte_, first_ ? 2u : 1u);                     \
-        o++;                                                                       \
-        if (++run == LZF_MAX_LIT) { K3_PATCH(hx, LZF_MAX_LIT - 1u); run = 0u; o++; } \
-    } while (0)
 
     while (__ballot(mode != K3_DONE)) {
         K3_CNT(8);
@@ -836,7 +664,7 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
                     word = (q > ms && q + 3u <= me) ? 0u : 0xFFFFFFFFu;         /* last match's interior */
                 } else {
                     const uint32_t d = cw - (q >> 5);
-                    word = d == 0u ? curw : (q >> 5) >= fl ? K3_RING(q >> 5) : bits[q >> 5];
+                    word = d == 0u ? curw : (q >> 5) >= fl ? EMIT_RING(q >> 5) : bits[q >> 5];
 #ifdef KT_TIMING
                     if (d && (q >> 5) < fl) K3_CNT(12);
 #endif
@@ -847,7 +675,7 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
                          * (q + 3 <= p + 2 < n and p >= 1: both inside the value),
                          * one memory wait instead of up to three */
                         const uint32_t x_ = dv_ld4(src + q) ^ (dv_ld4(src + p - 1u) >> 8);
-                        rel = (x_ & 0xFFFFFFu) == 0u ? 8u : RC_DIFF;
+                        rel = (x_ & 0xFFFFFFu) == 0u ? 8u : DV_CODE_DIFF;
                     }
                     mode = K3_DECIDE;
                 } else if (reln) {                                           /* the record's second link */
@@ -867,10 +695,10 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
                         mode = K3_DECIDE;
                     } else {
                         const uint32_t rq = rel;
-                        rel = k3_comb(rq, r1);
+                        rel = dv_comb(rq, r1, K3_EXACT);
                         q = y1;
                         if (r2 && p - y2 - 1u < LZF_WINDOW) {
-                            reln = k3_comb(rq, r2);
+                            reln = dv_comb(rq, r2, K3_EXACT);
                             qn = y2;
                         } else {
                             reln = 0u;
@@ -891,11 +719,11 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
                     ok = false;
                     mode = K3_DONE;
                 } else {
-                    K3_LITERAL(p);
+                    EMIT_LITERAL(p);
                     p++;
                     if ((p & 31u) == 0u) {
-                        K3_FLUSH_TO(cw);
-                        K3_RING(cw) = curw;
+                        EMIT_FLUSH_TO(cw);
+                        EMIT_RING(cw) = curw;
                         cw++;
                         curw = 0u;
                     }
@@ -927,13 +755,13 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
                             const uint32_t byte_ = (dv_sel4(W, x_ >> 2) >> (8u * (x_ & 3u))) & 0xFFu;
                             const bool first_ = run == 0u;
                             hx = first_ ? 4u * fw + accn : hx;
-                            K3_PUT(first_ ? byte_ << 8 : byte_, first_ ? 2u : 1u);
+                            EMIT_PUT(first_ ? byte_ << 8 : byte_, first_ ? 2u : 1u);
                             o++;
-                            if (++run == LZF_MAX_LIT) { K3_PATCH(hx, LZF_MAX_LIT - 1u); run = 0u; o++; }
+                            if (++run == LZF_MAX_LIT) { EMIT_PATCH(hx, LZF_MAX_LIT - 1u); run = 0u; o++; }
                             p++;
                             if ((p & 31u) == 0u) {
-                                K3_FLUSH_TO(cw);
-                                K3_RING(cw) = curw;
+                                EMIT_FLUSH_TO(cw);
+                                EMIT_RING(cw) = curw;
                                 cw++;
                                 curw = 0u;
                             }
@@ -950,7 +778,7 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
                     m = rel + 1u < lim ? rel + 1u : lim;
                     mode = K3_EMIT;
                 } else {
-                    k = rel == RC_LONG ? 8u : 3u;
+                    k = rel == DV_CODE_LONG ? 8u : 3u;
                     mode = K3_EXTEND;
                 }
             }
@@ -976,7 +804,7 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
         /* ---- the back-reference -------------------------------------------- */
         if (mode == K3_EMIT) {
             const uint32_t off = p - q - 1u;
-            if (run) K3_PATCH(hx, run - 1u);                             /* close the run */
+            if (run) EMIT_PATCH(hx, run - 1u);                             /* close the run */
             else o--;                                                    /* undo empty run */
             if (o + 4u >= cap) {                                         /* src/lzf_c.c:176 */
                 ok = false;
@@ -984,7 +812,7 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
             } else {
                 const uint32_t L = m - 2u;
                 const bool two = L < 7u;
-                K3_PUT(two ? ((off >> 8) | (L << 5)) | ((off & 0xFFu) << 8)
+                EMIT_PUT(two ? ((off >> 8) | (L << 5)) | ((off & 0xFFu) << 8)
                            : (0xE0u | (off >> 8)) | ((L - 7u) << 8) | ((off & 0xFFu) << 16),
                        two ? 2u : 3u);
                 o += two ? 2u : 3u;
@@ -1006,12 +834,12 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
                         const uint32_t wo = curw | (w1 == cw ? b1 : 0u) | (w2 == cw ? b2 : 0u);
                         const uint32_t wn = (w1 == nw ? b1 : 0u) | (w2 == nw ? b2 : 0u);
                         const uint32_t wm = (w1 != cw && w1 != nw ? b1 : 0u) | (w2 != cw && w2 != nw ? b2 : 0u);
-                        K3_FLUSH_TO(cw);
-                        K3_RING(cw) = wo;
+                        EMIT_FLUSH_TO(cw);
+                        EMIT_RING(cw) = wo;
                         /* words cw+1 .. nw-2 are all interior (0), nw-1 holds tails */
                         for (uint32_t w = cw + 1u; w < nw; w++) {
-                            K3_FLUSH_TO(w);
-                            K3_RING(w) = w + 1u == nw ? wm : 0u;
+                            EMIT_FLUSH_TO(w);
+                            EMIT_RING(w) = w + 1u == nw ? wm : 0u;
                         }
                         curw = wn;
                         cw = nw;
@@ -1020,12 +848,6 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
                 }
             }
         }
-#ifdef KT_ENDMODE   /* diagnostics: lanes that end an iteration mid-step, by mode */
-        k3c[4] += mode == K3_RESOLVE;
-        k3c[5] += mode == K3_DECIDE;
-        k3c[6] += mode == K3_EXTEND;
-        k3c[7] += mode == K3_EMIT;
-#endif
     }
 #ifdef KT_TIMING
     k3c[1] = __builtin_amdgcn_s_memtime() - k3t0;
@@ -1035,28 +857,11 @@ __global__ __launch_bounds__(K3_THREADS, K3_MINB) void lzf_parse_rec_kernel(LzfB
 #undef K3_CNT
     if (!ok || o + 3u > cap) { bt.out_len[v] = 0u; return; }          /* src/lzf_c.c:276 */
     while (p < n) {                                                   /* src/lzf_c.c:279-288 */
-        K3_LITERAL(p);
+        EMIT_LITERAL(p);
         p++;
     }
-    if (run) K3_PATCH(hx, run - 1u);
-    else o--;
-    for (uint32_t i = fs; i < fw; i++) {
-        const uint32_t wv = i == fs ? pb0 : i == fs + 1u ? pb1 : pb2;
-        if (i == 0u && dm != 0u)
-            for (uint32_t t = dm; t < 4u; t++) da[t] = (uint8_t)(wv >> (8u * t));
-        else
-            *(uint32_t *)(da + 4u * i) = wv;
-    }
-    for (uint32_t t = 0; t < accn; t++)
-        if (4u * fw + t >= dm) da[4u * fw + t] = (uint8_t)(acc >> (8u * t));
+    EMIT_FINISH();
     bt.out_len[v] = o;
-#undef K3_PUT
-#undef K3_STORE16
-#undef K3_PATCH
-#undef K3_BYTE
-#undef K3_LITERAL
-#undef K3_RING
-#undef K3_FLUSH_TO
 }
 
 /* ---- launcher ------------------------------------------------------------ */

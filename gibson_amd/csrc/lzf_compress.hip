@@ -40,7 +40,7 @@
  * Nothing is ever written at or past out_cap; the return value (0 or the
  * stream length) and the stream are identical to the reference's.
  */
-#include "lzf_internal.h"
+#include "lzf_dev.h"
 
 #define CW_LANES     64u
 #ifndef CW_HBITS
@@ -86,33 +86,6 @@ __device__ __forceinline__ uint64_t lanemask_lt(uint32_t i)
 __device__ __forceinline__ uint64_t range_mask(uint32_t lo, uint32_t hi)   /* bits [lo, hi) */
 {
     return lanemask_lt(hi) & ~lanemask_lt(lo);
-}
-
-__device__ __forceinline__ uint32_t slot_of(uint32_t tri)
-{
-    uint32_t b0 = tri & 0xFFu, b1 = (tri >> 8) & 0xFFu, b2 = (tri >> 16) & 0xFFu;
-    return (((b0 << 8) | b1) - 5u * ((b1 << 8) | b2)) & 0xFFFFu;
-}
-
-/* Order-preserving LDS hand-off between the lanes of the (single-wave)
- * workgroup: LDS ops of one wave execute in order, so only the compiler
- * must not move memory operations across this point. */
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-/* Inclusive prefix sum over the 64 lanes (DPP row shifts + row broadcasts). */
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x)
-{
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false); /* row_shr:1 */
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false); /* row_shr:2 */
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false); /* row_shr:4 */
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false); /* row_shr:8 */
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false); /* row_bcast:15 */
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false); /* row_bcast:31 */
-    return x;
 }
 
 /* Bucket-head entry: position of the latest inserted position of the
@@ -187,7 +160,6 @@ __device__ void cw_fill(const CwLds<HeadT, WRAP> &L, const uint8_t *src, uint32_
     }
 }
 
-__device__ __forceinline__ uint32_t slot_mix(uint32_t s) { return (s * 40503u) & 0xFFFFu; }
 __device__ __forceinline__ uint32_t bucket_of(uint32_t sm) { return sm >> (16 - CW_HBITS); }
 __device__ __forceinline__ uint32_t ident_of(uint32_t sm) { return sm & (CW_T1 - 1u); }
 __device__ __forceinline__ uint32_t filter_bit(uint32_t id) { return 1u << (id & 7u); }
@@ -253,7 +225,7 @@ __device__ __forceinline__ uint32_t cw_lookup(const CwLds<HeadT, WRAP> &L, HeadT
         if (same) return q;
         if (d == 0u) break;                       /* skip q's run of its slot */
         q -= d;
-        same = slot_of(L.rd4(q) & 0xFFFFFFu) == s;
+        same = dv_slot(L.rd4(q) & 0xFFFFFFu) == s;
         d = L.chain[L.ci(q)];
     }
     return 0xFFFFFFFFu;
@@ -304,7 +276,7 @@ __device__ __forceinline__ void cw_walk_step(const CwLds<HeadT, WRAP> &L, uint32
 {
     act = act && d != 0u;
     q = act ? q - d : q;
-    const uint32_t sq = slot_of(L.rd4(q) & 0xFFFFFFu);
+    const uint32_t sq = dv_slot(L.rd4(q) & 0xFFFFFFu);
     d = L.chain[L.ci(q)];
     act = act && p - q <= LZF_WINDOW;
     if (act && sq == s) T = q;
@@ -406,8 +378,8 @@ __global__ __launch_bounds__(64) void lzf_compress_window_kernel(LzfBatch bt, ui
         const uint32_t p = P + lane;
         const bool valid = lane < lim_lane;
         const uint32_t tri = L.rd4(p) & 0xFFFFFFu;
-        const uint32_t s = slot_of(tri);
-        const uint32_t sm = slot_mix(s);          /* bijective 16-bit mix of the slot */
+        const uint32_t s = dv_slot(tri);
+        const uint32_t sm = dv_mix(s);          /* bijective 16-bit mix of the slot */
         const uint32_t b = bucket_of(sm);
         const uint32_t k1 = ident_of(sm);
         /* Lanes past lim_lane take part unconditionally (no exec-mask
@@ -421,9 +393,9 @@ __global__ __launch_bounds__(64) void lzf_compress_window_kernel(LzfBatch bt, ui
         atomicOr(&L.t1[k1], me);
         atomicOr(&L.t2[k2], me);
         atomicOr(&L.t3[k3], me);
-        wave_lds_fence();
+        dv_wave_fence();
         const uint64_t M1 = L.t1[k1], M2 = L.t2[k2], M3 = L.t3[k3];
-        wave_lds_fence();
+        dv_wave_fence();
         L.t1[k1] = 0ull;
         L.t2[k2] = 0ull;
         L.t3[k3] = 0ull;
@@ -649,7 +621,7 @@ __global__ __launch_bounds__(64) void lzf_compress_window_kernel(LzfBatch bt, ui
         const uint32_t nf = 1u + R + (R >> 5);                    /* relative to H0 of seg */
         const uint32_t Tr = nf - ((R & 31u) == 0u ? 1u : 0u);
         const uint32_t delta = (visited && isM) ? Tr + tlen : 0u;
-        const uint32_t incl = wave_incl_sum(delta);
+        const uint32_t incl = dv_wave_incl_sum(delta);
         const uint32_t myH0 = H0 + incl - delta;
         /* Each visited lane stores up to four bytes, as four unconditional
          * stores under one exec mask: an unused store repeats the lane's
@@ -726,7 +698,7 @@ __global__ __launch_bounds__(64) void lzf_compress_window_kernel(LzfBatch bt, ui
                 if (last) head_set(L.head, b, k1, p);
             }
         }
-        wave_lds_fence();
+        dv_wave_fence();
         if (tx0 != 0xFFFFFFFFu || tx1 != 0xFFFFFFFFu) {
             /* the exit match's tails past the window: lane 0 inserts tx0,
              * lane 1 tx1 (after tx0: when both hit one bucket, tx0 is tx1's
@@ -735,7 +707,7 @@ __global__ __launch_bounds__(64) void lzf_compress_window_kernel(LzfBatch bt, ui
             const bool act = lane < 2u && t != 0xFFFFFFFFu;
             uint32_t bt = 0xFFFFFFFFu, idt = 0, y = 0xFFFFFFFFu;
             if (act) {
-                const uint32_t smt = slot_mix(slot_of(L.rd4(t) & 0xFFFFFFu));
+                const uint32_t smt = dv_mix(dv_slot(L.rd4(t) & 0xFFFFFFu));
                 bt = bucket_of(smt);
                 idt = ident_of(smt);
                 const HeadT ht = L.head[bt];
@@ -757,7 +729,7 @@ __global__ __launch_bounds__(64) void lzf_compress_window_kernel(LzfBatch bt, ui
                 head_mark(L.head, bt, idt);
                 if (lane == 1 || tx1 == 0xFFFFFFFFu || b1t != bt) head_set(L.head, bt, idt, t);
             }
-            wave_lds_fence();
+            dv_wave_fence();
         }
         CW_PHASE(7);
         P = Pn;

@@ -33,7 +33,7 @@
  * workgroup barrier per round); a consumer runs step 4.  `tokpar64` (one wave
  * does everything) stays as the single-wave form.
  */
-#include "lzf_internal.h"
+#include "lzf_dev.h"
 
 #define CD_LANES   64u
 #define CD_ROUND   128u             /* input bytes whose token starts one round covers */
@@ -98,12 +98,6 @@ __device__ __forceinline__ uint4 cd_shr16(uint4 v, uint32_t d)
  * __ballot takes an int, which can cost a select and a compare per use) */
 __device__ __forceinline__ uint64_t cd_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
-__device__ __forceinline__ void cd_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 #ifdef CD_TIMING
 /* diagnostic build: per role, cycles working and cycles waiting at the
  * pipe's barriers, summed over waves (lzf_gpu_dec_tstat) */
@@ -136,17 +130,6 @@ __device__ __forceinline__ void cd_barrier(uint64_t *tw = nullptr)
 #endif
 }
 
-__device__ __forceinline__ uint32_t cd_incl_sum(uint32_t x)
-{
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);
-    return x;
-}
-
 __device__ __forceinline__ uint32_t cd_rl(uint32_t v, uint32_t l)
 {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
@@ -173,7 +156,7 @@ __device__ __forceinline__ void cd_stage(uint8_t *inr, const uint8_t *src, uint3
         const uint32_t x = loaded + 16u * lane;   /* loaded is a multiple of 16 here */
         if (x < to) *(uint4 *)(inr + (x & (IN_RING - 1u))) = cd_ld16(src + x, to - x);
         loaded = to;
-        cd_fence();
+        dv_wave_fence();
     }
 }
 
@@ -236,7 +219,7 @@ __device__ __forceinline__ uint32_t cd_discover_lds(const uint8_t *inr, uint32_t
         if (ipa + 1u + tb >= in_len) nb = 255u;
     }
     *(uint16_t *)(jt + pa) = (uint16_t)(na | (nb << 8));
-    cd_fence();
+    dv_wave_fence();
     uint32_t x = 0;
 #pragma unroll
     for (uint32_t b = 0; b < 6u; b++) {
@@ -244,9 +227,9 @@ __device__ __forceinline__ uint32_t cd_discover_lds(const uint8_t *inr, uint32_t
         if (b < 5u) {
             na = jt[na];
             nb = jt[nb];
-            cd_fence();
+            dv_wave_fence();
             *(uint16_t *)(jt + pa) = (uint16_t)__builtin_amdgcn_perm(nb, na, 0x0c0c0400u);   /* na | nb << 8 */
-            cd_fence();
+            dv_wave_fence();
         }
         x = ((lane >> b) & 1u) ? jx : x;
     }
@@ -281,7 +264,7 @@ __device__ __forceinline__ CdRound cd_decode(const uint8_t *inr, uint32_t imask,
     const uint32_t olen = lit ? c + 1u : (c >> 5) + (l7 ? b1 : 0u) + 2u;
     const uint32_t lsrc = ip + 1u;                      /* literals only */
     const uint32_t ol = tok ? olen : 0u;
-    const uint32_t incl = cd_incl_sum(ol);
+    const uint32_t incl = dv_wave_incl_sum(ol);
     CdRound r;
     r.rel = incl - ol;
     const uint32_t Ot = O + r.rel;                      /* output offset of my token */
@@ -412,7 +395,7 @@ __device__ __forceinline__ void cd_output(uint8_t *lds, uint32_t outr_off, uint3
     uint32_t m = 0u;
     if (MA && total) {
         mark[min(Otm - O, CD_LANES)] = (MT)Otm;       /* without a branch */
-        cd_fence();
+        dv_wave_fence();
         m = mark[lane];
     }
     for (uint32_t g = 0; g < total; g += CD_LANES) {
@@ -420,7 +403,7 @@ __device__ __forceinline__ void cd_output(uint8_t *lds, uint32_t outr_off, uint3
         const uint32_t o = gb + lane;
         if (!MA) {
             mark[min(Otm - gb, CD_LANES)] = (MT)Otm;
-            cd_fence();
+            dv_wave_fence();
             m = mark[lane];
         }
         const bool mine = (MT)m == (MT)o;   /* 16-bit marks: a stream's output stays below 65536 */
@@ -435,9 +418,9 @@ __device__ __forceinline__ void cd_output(uint8_t *lds, uint32_t outr_off, uint3
             /* the next group's marks, in the shadow of this group's LDS
              * chain (they depend on nothing it writes; a group past the
              * round marks slot 64 only: no token starts there) */
-            cd_fence();
+            dv_wave_fence();
             mark[min(Otm - (gb + CD_LANES), CD_LANES)] = (MT)Otm;
-            cd_fence();
+            dv_wave_fence();
             m = mark[lane];
         }
         const bool lit = (int32_t)tInf < 0;
@@ -494,7 +477,7 @@ __device__ __forceinline__ void cd_output(uint8_t *lds, uint32_t outr_off, uint3
         }
         const bool live = lane < total - g;
         lds[outr_off + (live ? o & omask : sink_off - outr_off)] = (uint8_t)ent;   /* the sink lies past the window */
-        cd_fence();
+        dv_wave_fence();
         {
             const uint32_t done = g + CD_LANES <= total ? gb + CD_LANES : O + total;
             if (done - F >= unit) {
@@ -664,7 +647,7 @@ __global__ __launch_bounds__(64) void lzf_decompress_tokpar_kernel(LzfBatch bt, 
                     *(uint4 *)(inr + (x & (CD_IN_RING1 - 1u))) = cd_ld16(src + x, to - x);
                 }
                 loaded = to;
-                cd_fence();
+                dv_wave_fence();
                 /* the piece after it */
                 const uint32_t to2 = min(loaded + STAGE, avail);
                 const uint32_t x2 = loaded + 16u * lane;
@@ -722,7 +705,7 @@ __device__ __forceinline__ void cd_stage_pipe(uint8_t *inr, const uint8_t *src, 
             *(uint4 *)(inr + (x & (CD_IN_RINGP - 1u))) = v;
         }
         loaded = to;
-        cd_fence();
+        dv_wave_fence();
     }
 }
 
@@ -812,7 +795,7 @@ __global__ __launch_bounds__(128) void lzf_decompress_pipe_kernel(LzfBatch bt, u
                     }
                     loaded = max(loaded, qt);
                     qf = qt = 0u;
-                    cd_fence();
+                    dv_wave_fence();
                 }
             } else if (CD_PREF && pend) {
                 const uint32_t px = loaded + 16u * lane;
@@ -821,7 +804,7 @@ __global__ __launch_bounds__(128) void lzf_decompress_pipe_kernel(LzfBatch bt, u
                 }
                 loaded = pto;
                 pend = false;
-                cd_fence();
+                dv_wave_fence();
             }
             cd_stage_pipe(inr, src, base, avail, loaded, lane);
             if (CD_PREF2) {

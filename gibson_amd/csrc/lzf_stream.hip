@@ -34,38 +34,6 @@
 #define KS_PF     4u                         /* blocks of input in flight (the step loop's unroll) */
 #define KS_CL     2u                         /* steps from the agreement load to its use */
 
-__device__ __forceinline__ uint32_t ks_lds_addr(const void *p)
-{
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-
-/* the block's 15 exchanges in window (= stream position) order, one wait at
- * the end; later groups take earlier results as in-out operands so nothing
- * reads a result before the wait (lzf_wparse.hip has the same step) */
-#define KSX(i_) "ds_mskor_rtn_b32 %" #i_ ", %[a" #i_ "], %[m" #i_ "], %[d" #i_ "]\n\t"
-#define KSI(i_, o_) [a##i_] "v"(a[(o_) + i_]), [m##i_] "v"(m[(o_) + i_]), [d##i_] "v"(d[(o_) + i_])
-__device__ __forceinline__ void ks_xchg15(uint32_t (&r)[15], const uint32_t (&a)[15], const uint32_t (&m)[15],
-                                          const uint32_t (&d)[15])
-{
-    asm volatile(KSX(0) KSX(1) KSX(2) KSX(3) KSX(4)
-                 : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4])
-                 : KSI(0, 0), KSI(1, 0), KSI(2, 0), KSI(3, 0), KSI(4, 0)
-                 : "memory");
-    asm volatile(KSX(0) KSX(1) KSX(2) KSX(3) KSX(4)
-                 : "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7]), "=&v"(r[8]), "=&v"(r[9]),
-                   "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4])
-                 : KSI(0, 5), KSI(1, 5), KSI(2, 5), KSI(3, 5), KSI(4, 5)
-                 : "memory");
-    asm volatile(KSX(0) KSX(1) KSX(2) KSX(3) KSX(4) "s_waitcnt lgkmcnt(0)"
-                 : "=&v"(r[10]), "=&v"(r[11]), "=&v"(r[12]), "=&v"(r[13]), "=&v"(r[14]),
-                   "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]),
-                   "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9])
-                 : KSI(0, 10), KSI(1, 10), KSI(2, 10), KSI(3, 10), KSI(4, 10)
-                 : "memory");
-}
-#undef KSX
-#undef KSI
-
 /* windows of a value: positions 0 .. n-3 in windows of 64.  A value the
  * parse refuses gets none, and so does one of fewer than 8 bytes (its few
  * words come from ks_tiny): every window's loads are then plain clamped
@@ -90,7 +58,7 @@ __device__ __noinline__ void ks_tiny(const uint8_t *src, uint32_t n, uint16_t *c
         if (q != 0xFFFFFFFFu && q > 0u) {                   /* position 0 is never a ref */
             uint32_t k = 0u;
             while (k < 8u && p + k < n && b[q + k] == b[p + k]) k++;
-            word = ((k < 3u ? 1u : k >= 8u ? 7u : k - 1u) << 13) | (p - q - 1u);
+            word = (dv_code(k) << 13) | (p - q - 1u);
         }
         cand[p] = (uint16_t)word;
     }
@@ -153,28 +121,14 @@ extern "C" int lzf_gpu_debug_ks(unsigned long long *out16, int reset)
 #define KS_TM(i) ((void)0)
 #endif
 
-/* agreement code of k equal bytes (src/lzf_c.c:151-158 and the parse's
- * walk): 1 differ within 3, 2..6 exactly k (3..7), 7 at least 8 */
-__device__ __forceinline__ uint32_t ks_code(uint32_t k) { return k < 3u ? 1u : (k >= 8u ? 7u : k - 1u); }
-
-/* agreement of 8 bytes a (at p) and b (at q), at most avail = n - p */
-#ifndef KS_FFBL
-#define KS_FFBL 1
-#endif
+/* agreement of 8 bytes a (at p) and b (at q), at most avail = n - p.
+ * v_ffbl gives the lowest set bit or ~0 for none: min3(ffbl(lo), ffbl(hi) | 32,
+ * 64) is the first differing bit, 64 for none (round 5: no 64-bit compare and
+ * select) */
 __device__ __forceinline__ uint32_t ks_agree(uint2 a, uint2 b, uint32_t avail)
 {
-#if KS_FFBL
-    /* v_ffbl gives the lowest set bit or ~0 for none: min3(ffbl(lo),
-     * ffbl(hi) | 32, 64) is the first differing bit, 64 for none (round 5:
-     * no 64-bit compare and select) */
-    uint32_t fl, fh;
-    asm("v_ffbl_b32 %0, %1" : "=v"(fl) : "v"(a.x ^ b.x));
-    asm("v_ffbl_b32 %0, %1" : "=v"(fh) : "v"(a.y ^ b.y));
+    const uint32_t fl = dv_ffbl(a.x ^ b.x), fh = dv_ffbl(a.y ^ b.y);
     const uint32_t k = min(min(fl, fh | 32u), 64u) >> 3;
-#else
-    const uint64_t x = ((uint64_t)(a.y ^ b.y) << 32) | (uint64_t)(a.x ^ b.x);
-    const uint32_t k = x ? (uint32_t)__builtin_ctzll(x) >> 3 : 8u;
-#endif
     return k < avail ? k : avail;
 }
 
@@ -318,7 +272,7 @@ __global__ __launch_bounds__(KS_THR) void lzf_cand_stream_kernel(LzfBatch bt, ui
         c_q[i] = c_q2[i] = 0u;
         c_a[i] = c_b[i] = c_b2[i] = make_uint2(0u, 0u);
     }
-    const uint32_t tb = ks_lds_addr(T);
+    const uint32_t tb = dv_lds_addr(T);
 
 #ifdef KS_TIMING
     uint64_t ks_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -357,7 +311,7 @@ __global__ __launch_bounds__(KS_THR) void lzf_cand_stream_kernel(LzfBatch bt, ui
                         xd[i] = e.y;
                     }
                 }
-                ks_xchg15(xr, xa, xm, xd);
+                dv_xchg15(xr, xa, xm, xd);
 #pragma unroll
                 for (uint32_t i = 0; i < 15u; i++) Ok[64u * i + lane] = (uint16_t)(xr[i] >> hs[i]);
             }
@@ -377,13 +331,13 @@ __global__ __launch_bounds__(KS_THR) void lzf_cand_stream_kernel(LzfBatch bt, ui
                  * stale table entry names a position of another slot */
                 const uint32_t k1 = ks_agree(a, b, n - p);
                 const bool v1 = q != 0u && (k1 >= 3u || dv_slot(b.x) == sp);
-                uint32_t word = v1 ? (ks_code(k1) << 13) | (p - q - 1u) : 0u;
+                uint32_t word = v1 ? (dv_code(k1) << 13) | (p - q - 1u) : 0u;
                 if constexpr (REC) {
                     const uint32_t q2 = c_q2[CS];
                     const uint2 b2 = near_end ? ks_fix(c_b2[CS], n, q2) : c_b2[CS];
                     const uint32_t k2 = ks_agree(a, b2, n - p);
                     const bool v2 = v1 && q2 != 0u && (k2 >= 3u || dv_slot(b2.x) == sp);
-                    word |= v2 ? ((ks_code(k2) << 13) | (p - q2 - 1u)) << 16 : 0u;
+                    word |= v2 ? ((dv_code(k2) << 13) | (p - q2 - 1u)) << 16 : 0u;
                 }
                 if constexpr (REC)
                     ((uint32_t *)out)[(uint64_t)c_v[CS] * ostride + p] = word;

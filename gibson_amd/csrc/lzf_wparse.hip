@@ -65,55 +65,9 @@
 #define KQ_XCHG 1
 #endif
 
-__device__ __forceinline__ uint32_t kq_lds_addr(const void *p)
-{
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-
-/* the block's 15 exchanges, issued in window (= position) order with one
- * wait at the end.  The LDS runs one wave's same-address ds_mskor_rtn_b32
- * in lane order (tools/lds_mskor_order.hip; checked at run time by
- * lzf_selfcheck.hip), so each lane gets the latest earlier same-slot
- * position -- the table's or an earlier lane's -- and the highest lane's
- * position is what stays; and one wave's LDS operations execute in order,
- * so the table is updated in position order.  Three asm groups of five: the
- * later groups take the earlier results as in-out operands, so nothing reads
- * a result before the single wait. */
-#define KQ_X(i_) "ds_mskor_rtn_b32 %" #i_ ", %[a" #i_ "], %[m" #i_ "], %[d" #i_ "]\n\t"
-#define KQ_IN(i_, o_) [a##i_] "v"(a[(o_) + i_]), [m##i_] "v"(m[(o_) + i_]), [d##i_] "v"(d[(o_) + i_])
-__device__ __forceinline__ void kq_xchg15(uint32_t (&r)[15], const uint32_t (&a)[15], const uint32_t (&m)[15],
-                                          const uint32_t (&d)[15])
-{
-    asm volatile(KQ_X(0) KQ_X(1) KQ_X(2) KQ_X(3) KQ_X(4)
-                 : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4])
-                 : KQ_IN(0, 0), KQ_IN(1, 0), KQ_IN(2, 0), KQ_IN(3, 0), KQ_IN(4, 0)
-                 : "memory");
-    asm volatile(KQ_X(0) KQ_X(1) KQ_X(2) KQ_X(3) KQ_X(4)
-                 : "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7]), "=&v"(r[8]), "=&v"(r[9]),
-                   "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4])
-                 : KQ_IN(0, 5), KQ_IN(1, 5), KQ_IN(2, 5), KQ_IN(3, 5), KQ_IN(4, 5)
-                 : "memory");
-    asm volatile(KQ_X(0) KQ_X(1) KQ_X(2) KQ_X(3) KQ_X(4) "s_waitcnt lgkmcnt(0)"
-                 : "=&v"(r[10]), "=&v"(r[11]), "=&v"(r[12]), "=&v"(r[13]), "=&v"(r[14]),
-                   "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]),
-                   "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9])
-                 : KQ_IN(0, 10), KQ_IN(1, 10), KQ_IN(2, 10), KQ_IN(3, 10), KQ_IN(4, 10)
-                 : "memory");
-}
-#undef KQ_X
-#undef KQ_IN
-static_assert(KQ_WIN == 15u, "kq_xchg15 issues 15 windows");
-
-/* bytes p, p+1, p+2 (p + 3 <= n) with one 4-byte load moved back inside the
- * value near its end */
-__device__ __forceinline__ uint32_t kq_tri(const uint8_t *src, uint32_t n, uint32_t p)
-{
-    if (n >= 4u) {
-        const uint32_t at = p + 4u <= n ? p : n - 4u;
-        return dv_ld4(src + at) >> (8u * (p - at));
-    }
-    return (uint32_t)src[p] | ((uint32_t)src[p + 1u] << 8) | ((uint32_t)src[p + 2u] << 16);
-}
+/* the table step: the block's 15 lane-ordered exchanges in window (= position)
+ * order, one wait at the end (dv_xchg15, lzf_dev.h) */
+static_assert(KQ_WIN == 15u, "dv_xchg15 issues 15 windows");
 
 template <uint32_t V> struct KqIc { static constexpr uint32_t value = V; };
 
@@ -145,7 +99,7 @@ __global__ __launch_bounds__(KQ_THREADS) void lzf_cand_q1_kernel(LzfBatch bt, ui
 #pragma unroll
         for (uint32_t d = 0; d < KQ_PF; d++) {
             const uint32_t p = KQ_BLK * d + 64u * j + lane;
-            pf[d] = (w && p < np) ? kq_tri(src, n, p) : 0u;
+            pf[d] = (w && p < np) ? dv_tri(src, n, p) : 0u;
         }
         for (uint32_t k = tid; k < LZF_SLOTS / 8u; k += KQ_THREADS) ((uint4 *)T)[k] = make_uint4(0, 0, 0, 0);
         __syncthreads();
@@ -171,7 +125,7 @@ __global__ __launch_bounds__(KQ_THREADS) void lzf_cand_q1_kernel(LzfBatch bt, ui
                         xm[i] = (e[i].x & 1u) ? 0xFFFF0000u : 0x0000FFFFu;
                         xd[i] = e[i].y;
                     }
-                    kq_xchg15(xr, xa, xm, xd);
+                    dv_xchg15(xr, xa, xm, xd);
 #pragma unroll
                     for (uint32_t i = 0; i < 15u; i++)
                         Ok[64u * i + lane] = (uint16_t)(xr[i] >> ((e[i].x & 1u) << 4));
@@ -214,7 +168,7 @@ __global__ __launch_bounds__(KQ_THREADS) void lzf_cand_q1_kernel(LzfBatch bt, ui
                     /* a position past the value exchanges in its lane's own dummy */
                     const uint32_t h = act ? dv_slot(pf[PS]) : LZF_SLOTS + lane;
                     S[KQ_BLK * (t & 1u) + 64u * j + lane] =
-                        make_uint2((kq_lds_addr(T) + 4u * (h >> 1)) | (h & 1u), (p & 0xFFFFu) << ((h & 1u) << 4));
+                        make_uint2((dv_lds_addr(T) + 4u * (h >> 1)) | (h & 1u), (p & 0xFFFFu) << ((h & 1u) << 4));
 #else
                     /* the window's same-slot lanes from 16 ballots of the slot
                      * bits: the nearest earlier one (or none), and whether
@@ -236,7 +190,7 @@ __global__ __launch_bounds__(KQ_THREADS) void lzf_cand_q1_kernel(LzfBatch bt, ui
 #ifdef KQ_ABL_L     /* diagnostics: no input loads */
                 pf[PS] = lp * 2654435761u;
 #else
-                pf[PS] = lp < np ? kq_tri(src, n, lp) : 0u;
+                pf[PS] = lp < np ? dv_tri(src, n, lp) : 0u;
 #endif
             }
 #ifndef KQ_ABL_S    /* diagnostics: no barrier */

@@ -18,17 +18,18 @@ def _pack(values, align=16):
     return arena, np.array(offs, np.int64)
 
 
-def _caps_layout(caps, align=16):
-    offs, pos = [], 0
+def _caps_layout(caps, align=16, shift=0):
+    offs, pos = [], shift
     for c in caps:
         offs.append(pos)
         pos += (max(c, 1) + align - 1) // align * align
     return np.array(offs, np.int64), max(pos, 16)
 
 
-def gpu_compress(values, out_caps, dev="cuda", align=16):
+def gpu_compress(values, out_caps, dev="cuda", align=16, out_shift=0):
+    # out_shift: every output starts that many bytes past a multiple of align
     arena, in_off = _pack(values, align)
-    out_off, out_size = _caps_layout(out_caps, align)
+    out_off, out_size = _caps_layout(out_caps, align, out_shift)
     d_in = torch.from_numpy(arena).to(dev)
     d_in_off = torch.from_numpy(in_off).to(dev)
     d_in_len = torch.tensor([len(v) for v in values], dtype=torch.int32, device=dev)

@@ -304,6 +304,37 @@ def test_unaligned_arenas(oracle, generation, align):
     assert gpu_decompress(streams, [len(v) for v in origs], align=align) == [(v, 0) for v in origs]
 
 
+EMIT_LENS = [1, 2, 3, 4, 15, 16, 17, 31, 32, 33, 63, 64, 65, 96, 97]      # around LZF_MAX_LIT = 32
+
+
+@pytest.fixture(scope="module")
+def emit_cases(oracle):
+    # 130 values (two waves' lanes and a partial wave), the oracle once.  Rows
+    # of the 15 lengths: incompressible (the run header is patched behind the
+    # cursor at 32 literals) with the roomy and the tight cap, and two rows all
+    # one byte (matches that end mid-dword), one with each cap
+    vals, caps = [], []
+    for i in range(130):
+        n, row = EMIT_LENS[i % len(EMIT_LENS)], i // len(EMIT_LENS)
+        vals.append(bytes([0x41 + i % 7]) * n if row in (2, 5) else random.Random(0xE317 + i).randbytes(n))
+        caps.append(max(1, n - 4) if row in (1, 4, 5, 7) else n + n // 16 + 64)
+    return vals, caps, [oracle.compress(v, c) for v, c in zip(vals, caps)]
+
+
+@pytest.mark.parametrize("shift", [0, 1, 2, 3])
+@pytest.mark.parametrize("kernel", ["lane", "table"])
+def test_shared_emitter_headers_and_first_dword(emit_cases, monkeypatch, kernel, shift):
+    # both one-lane-per-value parses write through the one output cursor
+    # (lzf_emit.h): its run-header patch, its 16-byte stores and the first
+    # dword of an output that starts 0..3 bytes past a dword
+    from tests.gpu_batch import gpu_compress
+    monkeypatch.setenv("LZF_GPU_KERNEL", kernel)
+    vals, caps, exp = emit_cases
+    res = gpu_compress(vals, caps, align=4, out_shift=shift)
+    bad = [(i, len(vals[i]), caps[i]) for i, (a, b) in enumerate(zip(res, exp)) if a != b]
+    assert not bad, f"{len(bad)} mismatches; first (index, n, cap) {bad[:5]}"
+
+
 def test_lane_mid_class(oracle, monkeypatch, diag):
     # the mid-class lane kernels (values 4 KiB .. 64 KiB), opt-in
     from tests.gpu_batch import gpu_compress

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Cycles per phase of the wave-form parse kernel (diagnostic build with
--DKW_PHASES, tools/build_variant.sh), per value."""
+-DLZF_DIAG -DKW_PHASES over both lane files:
+SRC="lzf_lane.hip lzf_lane_diag.hip" tools/build_variant.sh phases -DLZF_DIAG -DKW_PHASES),
+per value."""
 import ctypes
 import os
 import sys
