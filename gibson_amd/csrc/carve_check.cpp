@@ -120,6 +120,16 @@ int main()
             fill("compact.w_live_src", a.w_live_src, n);
             settle("compact", n);
         });
+        at_every_misalignment(lzf_renumber_work_bytes(n), [&](void *work) {
+            LzfRenumberArgs a{};
+            a.count = n;
+            lzf_renumber_carve(a, work);
+            fill("renumber.w_state", a.w_state, SD_STATE_WORDS);
+            fill("renumber.w_tile_n", a.w_tile_n, nt);
+            fill("renumber.w_tile_b", a.w_tile_b, nt);
+            fill("renumber.w_tile_d", a.w_tile_d, nt);
+            settle("renumber", n);
+        });
         at_every_misalignment(lzf_select_work_bytes(n), [&](void *work) {
             LzfSelectArgs a{};
             a.count = n;

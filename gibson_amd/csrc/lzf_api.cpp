@@ -883,6 +883,60 @@ int lzf_gpu_store_compact(const uint8_t *src, uint64_t src_cap,
     return rc_of(lzf_launch_store_compact(a, (hipStream_t)stream));
 }
 
+uint64_t lzf_gpu_store_renumber_work_size(uint32_t count)
+{
+    return lzf_renumber_work_bytes(count);
+}
+
+/* the public struct's members, one for one */
+static LzfItemArrays arrays_of(const lzf_store_items *p)
+{
+    return LzfItemArrays{p->val_off, p->val_size, p->enc, p->val_len, p->key_off, p->key_len,
+                         p->item_time, p->item_ttl, p->item_lock, p->last_access};
+}
+
+int lzf_gpu_store_renumber(const lzf_store_items *src, uint32_t count,
+                           const uint8_t *src_keys, uint64_t src_keys_cap,
+                           const lzf_store_items *dst, uint32_t dst_cap,
+                           uint8_t *dst_keys, uint64_t dst_keys_cap, uint64_t *dst_keys_used,
+                           uint32_t *remap, uint64_t *report, uint32_t *status,
+                           void *work, void *stream)
+{
+    if (!src || !dst || !src_keys || !dst_keys || !dst_keys_used || !report || !status || !work) return LZF_GPU_EARG;
+    if (!count || !dst_cap || !src_keys_cap || !dst_keys_cap) return LZF_GPU_EARG;
+    const LzfItemArrays s = arrays_of(src), d = arrays_of(dst);
+    const void *sp[10] = {s.val_off, s.val_size, s.enc, s.val_len, s.key_off, s.key_len,
+                          s.item_time, s.item_ttl, s.item_lock, s.last_access};
+    const void *dp[10] = {d.val_off, d.val_size, d.enc, d.val_len, d.key_off, d.key_len,
+                          d.item_time, d.item_ttl, d.item_lock, d.last_access};
+    for (int k = 0; k < 10; k++) {
+        if (k < 6 && (!sp[k] || !dp[k])) return LZF_GPU_EARG;         /* the six required members */
+        if (!sp[k] != !dp[k]) return LZF_GPU_EARG;                    /* an optional member: in both or in neither */
+        if (sp[k] && sp[k] == dp[k]) return LZF_GPU_EARG;             /* a semispace copy: never in place */
+    }
+    if (!s.item_time != !s.item_ttl) return LZF_GPU_EARG;
+    /* the key arenas must not share a byte.  The ends saturate */
+    const uint64_t s0 = (uint64_t)(uintptr_t)src_keys, d0 = (uint64_t)(uintptr_t)dst_keys;
+    const uint64_t s1 = s0 + src_keys_cap < s0 ? ~0ull : s0 + src_keys_cap;
+    const uint64_t d1 = d0 + dst_keys_cap < d0 ? ~0ull : d0 + dst_keys_cap;
+    if (d0 < s1 && s0 < d1) return LZF_GPU_EARG;
+    if (const int rc = current_device_ok()) return rc;
+    LzfRenumberArgs a{};
+    a.src = s; a.dst = d; a.count = count; a.dst_cap = dst_cap;
+    a.src_keys = src_keys; a.src_keys_cap = src_keys_cap;
+    a.dst_keys = dst_keys; a.dst_keys_cap = dst_keys_cap; a.dst_keys_used = dst_keys_used;
+    a.remap = remap; a.report = report; a.status = status;
+    lzf_renumber_carve(a, work);
+    return rc_of(lzf_launch_store_renumber(a, (hipStream_t)stream));
+}
+
+int lzf_gpu_store_remap(uint32_t *idx, uint32_t n, const uint32_t *remap, uint32_t count, void *stream)
+{
+    if (!idx || !remap || !n || !count) return LZF_GPU_EARG;
+    if (const int rc = current_device_ok()) return rc;
+    return rc_of(lzf_launch_store_remap(idx, n, remap, count, (hipStream_t)stream));
+}
+
 uint64_t lzf_gpu_store_select_work_size(uint32_t count)
 {
     return lzf_select_work_bytes(count);
@@ -1209,6 +1263,23 @@ int lzf_gpu_key_index_insert(void *table, uint32_t slots, uint32_t *used,
     a.enc = enc; a.count = count; a.first = first; a.n = n;
     a.result = result; a.status = status;
     return rc_of(lzf_launch_kidx_insert(a, (hipStream_t)stream));
+}
+
+int lzf_gpu_key_index_rebuild(void *table, uint32_t slots, uint32_t *used,
+                              const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                              uint8_t *enc, uint32_t count,
+                              uint64_t *result, uint32_t *status, void *stream)
+{
+    if (!table || !used || !keys || !key_off || !key_len || !enc || !result || !status) return LZF_GPU_EARG;
+    if (!count) return LZF_GPU_EARG;
+    if (!lzf_kidx_slots_ok(slots) || ((uintptr_t)table & 7u)) return LZF_GPU_EARG;
+    if (const int rc = current_device_ok()) return rc;
+    LzfKidxArgs a{};
+    a.table = table; a.slots = slots; a.used = used;
+    a.keys = keys; a.key_off = key_off; a.key_len = key_len;
+    a.enc = enc; a.count = count; a.first = 0u; a.n = count;
+    a.result = result; a.status = status;
+    return rc_of(lzf_launch_kidx_rebuild(a, (hipStream_t)stream));
 }
 
 int lzf_gpu_key_index_lookup(const void *table, uint32_t slots,

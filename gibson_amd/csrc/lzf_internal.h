@@ -116,6 +116,42 @@ struct LzfCompactArgs {
     uint64_t *w_state, *w_tile_n, *w_tile_b, *w_tile_d, *w_live_dst, *w_live_src;
 };
 
+/* one set of the store's ten item arrays, device pointers, member for member
+ * the public lzf_store_items: the renumbering reads one set and writes another.
+ * item_time and item_ttl are given or NULL together; item_lock and last_access
+ * may be NULL */
+struct LzfItemArrays {
+    uint64_t *val_off;
+    uint32_t *val_size;
+    uint8_t *enc;
+    uint32_t *val_len;
+    uint64_t *key_off;
+    uint32_t *key_len;
+    int64_t *item_time;
+    int32_t *item_ttl;
+    int64_t *item_lock;
+    int64_t *last_access;
+};
+
+/* the renumbering of the live items into a second set of arrays and a second
+ * key arena (lzf_renumber.hip); device pointers.  src is only read */
+struct LzfRenumberArgs {
+    LzfItemArrays src, dst;
+    uint32_t count, dst_cap;
+    const uint8_t *src_keys;
+    uint64_t src_keys_cap;
+    uint8_t *dst_keys;
+    uint64_t dst_keys_cap;
+    uint64_t *dst_keys_used;
+    uint32_t *remap;
+    uint64_t *report;
+    uint32_t *status;
+    /* work area (lzf_renumber_layout): per scan tile the live count (top bit:
+     * a live key out of range), the live key bytes and the dead items' key
+     * bytes; after the carry the first two hold the sums of the tiles before */
+    uint64_t *w_state, *w_tile_n, *w_tile_b, *w_tile_d;
+};
+
 /* the prefix select over the store's keys (lzf_mget.hip); device pointers */
 struct LzfSelectArgs {
     const uint8_t *keys;
@@ -375,6 +411,13 @@ hipError_t lzf_launch_store_usage(LzfCompactArgs &a, hipStream_t s);
 hipError_t lzf_launch_store_compact(LzfCompactArgs &a, hipStream_t s);
 uint64_t lzf_compact_work_bytes(uint32_t count);
 void lzf_compact_carve(LzfCompactArgs &a, void *work);
+/* the renumbering (lzf_renumber.hip): the live items, dense and in order, into
+ * a second set of item arrays with their keys packed into a second arena; and
+ * an index list from before it translated through its remap */
+hipError_t lzf_launch_store_renumber(LzfRenumberArgs &a, hipStream_t s);
+hipError_t lzf_launch_store_remap(uint32_t *idx, uint32_t n, const uint32_t *remap, uint32_t count, hipStream_t s);
+uint64_t lzf_renumber_work_bytes(uint32_t count);
+void lzf_renumber_carve(LzfRenumberArgs &a, void *work);
 /* the operators over the store (lzf_mget.hip): the prefix select into an
  * index list, and MGET (`decode` over the gathered entries, in place in the
  * frame), COUNT and MTTL over an index list */
@@ -431,6 +474,9 @@ bool lzf_kidx_slots_ok(uint32_t slots);
 uint64_t lzf_kidx_table_bytes(uint32_t slots);
 uint32_t lzf_kidx_home(const uint8_t *key, uint32_t len, uint32_t slots);
 hipError_t lzf_launch_kidx_insert(LzfKidxArgs &a, hipStream_t s);
+/* the table and *used cleared, then the insert of [0, count), FULL judged on
+ * the items the insert will not skip */
+hipError_t lzf_launch_kidx_rebuild(LzfKidxArgs &a, hipStream_t s);
 hipError_t lzf_launch_kidx_lookup(LzfKidxArgs &a, const uint8_t *qkeys, const uint64_t *q_off, const uint32_t *q_len,
                                   uint32_t nq, uint32_t *idx, hipStream_t s);
 /* value moves between mapped host memory and device arenas (lzf_hostio.hip):

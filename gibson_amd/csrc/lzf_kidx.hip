@@ -36,6 +36,12 @@
  *   3. settle: with all claims visible, every live batch item looks its own
  *      key up; it is the mapping, or it is superseded and nulls itself.
  *
+ * rebuild: the table and *used cleared on the stream, then the insert of
+ * [0, count) with a decide of its own: a counting pass leaves the number of
+ * items the claim will not skip in result[0], and FULL is judged on that, not
+ * on count, so the dead tail a renumbering leaves costs no slot.  Claim and
+ * settle are the insert's, unchanged.
+ *
  * lookup: one thread per query key, one pass.
  *
  * The kernels are helpers of this translation unit, not part of the library's
@@ -173,6 +179,28 @@ __global__ void lzf_kidx_decide_kernel(LzfKidxArgs a)
 {
     const uint32_t bound = a.slots - a.slots / 4u;
     *a.status = (uint64_t)*a.used + a.n > bound ? (uint32_t)LZF_KIDX_FULL : (uint32_t)LZF_KIDX_OK;
+    a.result[0] = a.result[1] = a.result[2] = a.result[3] = 0ull;
+}
+
+/* rebuild: the items of [0, count) the insert will not skip, into result[0],
+ * which was zeroed on the stream before the launch; one add per workgroup */
+__global__ __launch_bounds__(SD_BLOCK) void lzf_kidx_count_kernel(LzfKidxArgs a)
+{
+    const uint64_t step = (uint64_t)gridDim.x * SD_BLOCK;
+    uint32_t takes = 0u;
+    for (uint64_t i = (uint64_t)blockIdx.x * SD_BLOCK + threadIdx.x; i < a.n; i += step)
+        if (a.enc[i] != (uint8_t)LZF_ENC_NULL && a.key_len[i]) takes++;
+    uint64_t v[3] = {takes, 0ull, 0ull};
+    if (!ki_block_sums(v)) return;
+    if (v[0]) atomicAdd((unsigned long long *)&a.result[0], (unsigned long long)v[0]);
+}
+
+/* rebuild's decide: the table and *used were cleared on the stream, so FULL is
+ * judged on the counted items alone, not on n -- a dead tail costs no slot */
+__global__ void lzf_kidx_decide_counted_kernel(LzfKidxArgs a)
+{
+    const uint32_t bound = a.slots - a.slots / 4u;
+    *a.status = a.result[0] > bound ? (uint32_t)LZF_KIDX_FULL : (uint32_t)LZF_KIDX_OK;
     a.result[0] = a.result[1] = a.result[2] = a.result[3] = 0ull;
 }
 
@@ -334,6 +362,20 @@ uint32_t lzf_kidx_home(const uint8_t *key, uint32_t len, uint32_t slots)
 hipError_t lzf_launch_kidx_insert(LzfKidxArgs &a, hipStream_t s)
 {
     hipLaunchKernelGGL(lzf_kidx_decide_kernel, dim3(1), dim3(1), 0, s, a);
+    hipLaunchKernelGGL(lzf_kidx_claim_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_kidx_settle_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+/* first == 0 and n == count.  The counting word is result[0]: no work area */
+hipError_t lzf_launch_kidx_rebuild(LzfKidxArgs &a, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(a.table, 0xFF, (size_t)lzf_kidx_table_bytes(a.slots), s);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(a.used, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(a.result, 0, 4 * sizeof(uint64_t), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(lzf_kidx_count_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(lzf_kidx_decide_counted_kernel, dim3(1), dim3(1), 0, s, a);
     hipLaunchKernelGGL(lzf_kidx_claim_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
     hipLaunchKernelGGL(lzf_kidx_settle_kernel, dim3(sd_sweep_grid(a.n)), dim3(SD_BLOCK), 0, s, a);
     return hipGetLastError();

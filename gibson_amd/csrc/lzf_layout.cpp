@@ -1,5 +1,5 @@
 /*
- * lzf_layout.cpp -- the sizes and the carves of the device store's nine work
+ * lzf_layout.cpp -- the sizes and the carves of the device store's ten work
  * areas, each from its one layout (lzf_store_layout.h): the size is the layout
  * measured plus the slack for aligning the caller's pointer (64 bytes for the
  * frame, 16 for the others, as ever), the carve is the layout over that
@@ -55,6 +55,15 @@ uint64_t lzf_compact_work_bytes(uint32_t count)
 }
 
 void lzf_compact_carve(LzfCompactArgs &a, void *work) { carved(a, lzf_compact_layout, work); }
+
+uint64_t lzf_renumber_work_bytes(uint32_t count)
+{
+    LzfRenumberArgs a{};
+    a.count = count;
+    return measured(a, lzf_renumber_layout, 16u);
+}
+
+void lzf_renumber_carve(LzfRenumberArgs &a, void *work) { carved(a, lzf_renumber_layout, work); }
 
 uint64_t lzf_select_work_bytes(uint32_t count)
 {

@@ -1,7 +1,7 @@
 /*
  * lzf_store_dev.h -- the toolkit of the device store's kernels (lzf_frame.hip,
  * lzf_store.hip, lzf_mget.hip, lzf_kidx.hip, lzf_ops.hip, lzf_mset.hip,
- * lzf_meta.hip, lzf_reply.hip), over the byte helpers of lzf_dev.h and the
+ * lzf_meta.hip, lzf_reply.hip, lzf_renumber.hip), over the byte helpers of lzf_dev.h and the
  * geometry of lzf_store_layout.h.  One copy of each: the pad and the "no
  * entry" class; the ballot count, the 64-bit wave sum and the wave leader's
  * add; the block scan and the carry scan over tile sums; put32, the reply
@@ -37,6 +37,26 @@ __device__ inline uint64_t sd_wave_sum(uint64_t x)
         x += ((uint64_t)hi << 32) | lo;
     }
     return x;
+}
+
+/* the wave's largest of one u64 per lane, in every lane */
+__device__ inline uint64_t sd_wave_max(uint64_t x)
+{
+    for (int d = 32; d > 0; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, d, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), d, 64);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        x = o > x ? o : x;
+    }
+    return x;
+}
+
+/* one lane's u64, in every lane */
+__device__ inline uint64_t sd_lane_u64(uint64_t x, int lane)
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, lane, 64);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), lane, 64);
+    return ((uint64_t)hi << 32) | lo;
 }
 
 /* the wave's leader adds the wave's count x, if any, to a result word: one

@@ -134,6 +134,18 @@ static inline void lzf_compact_layout(LzfCompactArgs &a, LzfCarver &c)
     a.w_live_src = c.take<uint64_t>(n);
 }
 
+/* renumber (lzf_renumber.hip): per-tile sums only -- the write and the key
+ * pack rescan their own tile, so nothing is kept per item */
+static inline void lzf_renumber_layout(LzfRenumberArgs &a, LzfCarver &c)
+{
+    const uint64_t nt = sd_tiles(a.count);
+    c.align(8);
+    a.w_state = c.take<uint64_t>(SD_STATE_WORDS);
+    a.w_tile_n = c.take<uint64_t>(nt);
+    a.w_tile_b = c.take<uint64_t>(nt);
+    a.w_tile_d = c.take<uint64_t>(nt);
+}
+
 /* select (lzf_mget.hip) */
 static inline void lzf_select_layout(LzfSelectArgs &a, LzfCarver &c)
 {

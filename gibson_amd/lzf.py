@@ -84,6 +84,10 @@ EXPORTS = (
     "lzf_gpu_store_replies_work_size",
     "lzf_gpu_store_replies",
     "lzf_host_reply_code",
+    "lzf_gpu_store_renumber_work_size",
+    "lzf_gpu_store_renumber",
+    "lzf_gpu_store_remap",
+    "lzf_gpu_key_index_rebuild",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -92,8 +96,11 @@ KIND_COMPRESS, KIND_DECOMPRESS = 0, 1
 
 # *status of set_store (include/lzf_gpu.h)
 STORE_OK, STORE_FULL, STORE_EWORK = 0, 1, 2
-# *status of store_compact only: a live item's bytes leave the source arena
+# *status of store_compact and store_renumber only: a live item's value bytes
+# (its key bytes) leave the source arena
 STORE_ERANGE = 3
+# remap of a dead item (store_renumber), and what store_remap leaves for one
+STORE_NO_INDEX = 0xFFFFFFFF
 # result[3] of store_mget (include/lzf_gpu.h)
 MGET_OK, MGET_NOT_FOUND, MGET_TOO_BIG, MGET_EDECODE = 0, 1, 2, 3
 # *status of key_index_insert (include/lzf_gpu.h)
@@ -228,6 +235,8 @@ def _load(path):
         _bind_store_mset(L)
     if hasattr(L, "lzf_gpu_store_replies"):
         _bind_store_replies(L)
+    if hasattr(L, "lzf_gpu_store_renumber"):
+        _bind_store_renumber(L)
     del i32
     _LOADED[path] = L
     return L
@@ -287,6 +296,28 @@ def _bind_store_lifecycle(L):
     L.lzf_gpu_store_compact_work_size.argtypes = [u32]
     L.lzf_gpu_store_compact.restype = ctypes.c_int
     L.lzf_gpu_store_compact.argtypes = [vp, u64, vp, vp, vp, u32, vp, u64, vp, vp, vp, vp, vp]
+
+
+class _StoreItems(ctypes.Structure):
+    """lzf_store_items of include/lzf_gpu.h: ten device pointers"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("val_off", "val_size", "enc", "val_len", "key_off", "key_len",
+                                               "item_time", "item_ttl", "item_lock", "last_access")]
+
+
+def _bind_store_renumber(L):
+    """The renumbering, the remap of an index list and the key index's
+    rebuild; absent from an older build given by LZF_HIP_LIB (the helpers
+    below then raise AttributeError)."""
+    u32, u64, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
+    items = vp                             # const lzf_store_items *, passed with ctypes.byref
+    L.lzf_gpu_store_renumber_work_size.restype = u64
+    L.lzf_gpu_store_renumber_work_size.argtypes = [u32]
+    L.lzf_gpu_store_renumber.restype = ctypes.c_int
+    L.lzf_gpu_store_renumber.argtypes = [items, u32, vp, u64, items, u32, vp, u64, vp, vp, vp, vp, vp, vp]
+    L.lzf_gpu_store_remap.restype = ctypes.c_int
+    L.lzf_gpu_store_remap.argtypes = [vp, u32, vp, u32, vp]
+    L.lzf_gpu_key_index_rebuild.restype = ctypes.c_int
+    L.lzf_gpu_key_index_rebuild.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
 
 
 def _bind_store_index(L):
@@ -706,6 +737,76 @@ def _opt_ptr(t):
     return ctypes.c_void_p(0) if t is None else _ptr(t)
 
 
+# ---- the renumbering: item indices and key bytes given back ---------------------
+
+class StoreItems:
+    """One set of the store's item arrays (lzf_store_items): val_off int64,
+    val_size int32, enc uint8, val_len int32, key_off int64, key_len int32,
+    and the optional item_time int64 with item_ttl int32, item_lock int64,
+    last_access int64.  Tensors of one length on one device; an absent
+    optional member is None."""
+    FIELDS = tuple(n for n, _ in _StoreItems._fields_)
+
+    def __init__(self, val_off, val_size, enc, val_len, key_off, key_len, item_time=None, item_ttl=None,
+                 item_lock=None, last_access=None):
+        self.val_off, self.val_size, self.enc, self.val_len = val_off, val_size, enc, val_len
+        self.key_off, self.key_len = key_off, key_len
+        self.item_time, self.item_ttl, self.item_lock, self.last_access = item_time, item_ttl, item_lock, last_access
+
+    @classmethod
+    def of(cls, items):
+        """``items`` itself, or a StoreItems from a dict with these names"""
+        return items if isinstance(items, cls) else cls(**dict(items))
+
+    def _struct(self):
+        s = _StoreItems()
+        for n in self.FIELDS:
+            t = getattr(self, n)
+            setattr(s, n, None if t is None else t.data_ptr())
+        return s
+
+
+def store_renumber_work(count, device):
+    """A scratch tensor for one store_renumber call over ``count`` items."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_renumber_work_size(int(count))), dtype=torch.uint8, device=device)
+
+
+def store_renumber(src, src_keys, dst, dst_keys, dst_keys_used, report, status, remap=None, work=None, stream=None):
+    """The live items of ``src`` (a StoreItems, or a dict with its names;
+    count = the length of src.enc) copied dense and in index order into
+    ``dst`` (dst_cap = the length of dst.enc), their key bytes packed from
+    ``src_keys`` into ``dst_keys`` from ``dst_keys_used[0]`` on, which is
+    advanced; the entries of dst past the live items become dead items.  The
+    key caps are the tensors' lengths.  remap (count elements, int32 read as
+    u32, optional): the new index per old item, STORE_NO_INDEX for a dead one.
+    report (4 elements, int64) = live items, their key bytes, dead items, the
+    key bytes the dead items still name; status (1 element, int32): STORE_OK,
+    or STORE_FULL / STORE_ERANGE with the call refused whole and nothing
+    written.  Value bytes do not move (store_compact does that) and the TTL
+    rule is not applied (store_expire does that).  No host wait; returns
+    ``work`` (store_renumber_work), which must outlive the stream's work."""
+    src, dst = StoreItems.of(src), StoreItems.of(dst)
+    n = src.enc.numel()
+    if work is None:
+        work = store_renumber_work(n, src.enc.device)
+    s, d = src._struct(), dst._struct()
+    rc = lib().lzf_gpu_store_renumber(ctypes.byref(s), n, _ptr(src_keys), int(src_keys.numel()), ctypes.byref(d),
+                                      int(dst.enc.numel()), _ptr(dst_keys), int(dst_keys.numel()),
+                                      _ptr(dst_keys_used), _opt_ptr(remap), _ptr(report), _ptr(status), _ptr(work),
+                                      _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_renumber")
+    return work
+
+
+def store_remap(idx, remap, stream=None):
+    """An index list from before a store_renumber translated in place through
+    its ``remap``: idx[k] = remap[idx[k]], STORE_NO_INDEX for an entry past the
+    old store (padding included).  No host wait."""
+    _check(lib().lzf_gpu_store_remap(_ptr(idx), int(idx.numel()), _ptr(remap), int(remap.numel()),
+                                     _stream_handle(stream)), "lzf_gpu_store_remap")
+
+
 def store_select_work(count, device):
     """A scratch tensor for one store_select_prefix call over ``count`` items."""
     import torch
@@ -862,6 +963,19 @@ def key_index_insert(table, used, keys, key_off, key_len, enc, first, n, result,
                                         _ptr(key_len), _ptr(enc), int(enc.numel()), int(first), int(n), _ptr(result),
                                         _ptr(status), _stream_handle(stream))
     _check(rc, "lzf_gpu_key_index_insert")
+
+
+def key_index_rebuild(table, used, keys, key_off, key_len, enc, result, status, stream=None):
+    """The table and ``used`` cleared on the stream, then every item of
+    [0, enc.numel()) inserted as key_index_insert does.  KIDX_FULL is judged
+    on the items the insert will not skip (live, with a key), counted on the
+    device, so the dead tail a store_renumber leaves costs nothing; on FULL
+    the table stays empty, used is 0 and no enc changes.  result and status as
+    key_index_insert.  No host wait."""
+    rc = lib().lzf_gpu_key_index_rebuild(_ptr(table), _key_index_slots(table), _ptr(used), _ptr(keys), _ptr(key_off),
+                                         _ptr(key_len), _ptr(enc), int(enc.numel()), _ptr(result), _ptr(status),
+                                         _stream_handle(stream))
+    _check(rc, "lzf_gpu_key_index_rebuild")
 
 
 def key_index_lookup(table, keys, key_off, key_len, enc, qkeys, q_off, q_len, idx, result, stream=None):

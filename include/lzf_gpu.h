@@ -356,9 +356,11 @@ int lzf_host_store_stats(const uint8_t *enc, const uint32_t *val_size, const uin
  * The store is the three arrays lzf_gpu_set_store writes and lzf_gpu_kv_frame
  * reads -- val_off[count] (u64), val_size[count] (u32), enc[count] (u8) --
  * over an arena.  An item is dead once enc[i] == LZF_ENC_NULL; every other
- * item is live (PLAIN, LZF, and NUMBER with its 8 stored bytes).  Item indices
- * are stable: nothing here renumbers items, so a host-side key -> index map
- * stays valid across a compaction.  Every pointer is device memory; every call
+ * item is live (PLAIN, LZF, and NUMBER with its 8 stored bytes).  Delete,
+ * expire, usage and compact keep item indices: a key -> index map stays valid
+ * across a compaction.  lzf_gpu_store_renumber is the one call that does not:
+ * it gives the dead items' indices and key bytes back, and hands out the remap
+ * from old to new indices.  Every pointer is device memory; every call
  * validates its arguments before any HIP call, is asynchronous on `stream`
  * and waits for nothing on the host, so SET, MGET, DEL / expire, compact and
  * SET again queue behind each other on one stream.
@@ -422,6 +424,87 @@ int lzf_gpu_store_compact(const uint8_t *src, uint64_t src_cap,
                           uint64_t *val_off, uint32_t *val_size, const uint8_t *enc, uint32_t count,
                           uint8_t *dst, uint64_t dst_cap, uint64_t *dst_used,
                           uint64_t *report, uint32_t *status, void *work, void *stream);
+
+/*
+ * Renumbering: a semispace copy of the live items from one set of item arrays
+ * (src, `count` items over the key arena src_keys) into a second set (dst,
+ * dst_cap entries over the key arena dst_keys).  Compaction gives value bytes
+ * back; this call gives item indices and key bytes back, which every overwrite,
+ * DEL and expiry otherwise burns for good.  Nothing is done in place.
+ *
+ * Live items.  Item i is live iff src->enc[i] != LZF_ENC_NULL.  The TTL rule is
+ * not applied here: run lzf_gpu_store_expire first.  The live item with the
+ * r-th smallest index becomes item r of dst: the order is stable, so among
+ * equal keys the highest index is the same item before and after.
+ *
+ * Copied members.  Every member is copied verbatim, val_off included: value
+ * bytes do not move, and the order of val_off is whatever it was until
+ * lzf_gpu_store_compact runs over the new arrays (before or after this call).
+ *
+ * Key bytes are packed densely in new-index order from base = *dst_keys_used:
+ * dst->key_off[r] = base + the key lengths of the live items before r, the
+ * bytes copied from src_keys + src->key_off[i].  Source offsets may be in any
+ * order, with gaps, or shared by several items.  A live item with key_len == 0
+ * is kept; it owns no bytes.
+ *
+ * The tail.  dst entries [live, dst_cap) become dead items: enc =
+ * LZF_ENC_NULL, val_size = val_len = key_len = 0, the time, ttl, lock and
+ * last_access members (where given) 0, and the offsets the end offsets, as
+ * compaction leaves ties: key_off = the new *dst_keys_used, val_off = the
+ * highest val_off + val_size of a live item (saturating; 0 without one).  A
+ * caller that does not know `live` on the host yet can therefore go on calling
+ * every operator with count = dst_cap.
+ *
+ * remap (count device u32, may be NULL): remap[i] = the new index of item i,
+ * or 0xFFFFFFFF for a dead item.  report (4 device u64) is filled whether the
+ * call is accepted or refused, from the values before the call: [0] live
+ * items, [1] their key bytes, [2] dead items, [3] the key bytes that dead
+ * items still name.  The host needs report[0] before its next
+ * lzf_gpu_set_store, as that call's `first`; nothing else has to be read back.
+ *
+ * *status (one device u32): LZF_STORE_OK; LZF_STORE_ERANGE when a live item's
+ * [key_off, key_off + key_len) leaves [0, src_keys_cap) (64-bit, wrap-safe; a
+ * dead item's key is never read or judged); otherwise LZF_STORE_FULL when
+ * live > dst_cap, or when base + the live key bytes exceed dst_keys_cap or
+ * wrap.  A refusal is whole: no byte of any dst array, of dst_keys or of remap
+ * is written and *dst_keys_used is unchanged.  On success *dst_keys_used =
+ * base + the live key bytes.  src and src_keys are never written.
+ *
+ * LZF_GPU_EARG, before any HIP call: a NULL struct; NULL among the six
+ * required members (val_off, val_size, enc, val_len, key_off, key_len), the
+ * key arenas, dst_keys_used, report, status or work; an optional member that
+ * is NULL in one of src / dst and not in the other; exactly one of item_time /
+ * item_ttl; count == 0, dst_cap == 0 or a zero key cap; [dst_keys, +
+ * dst_keys_cap) overlapping [src_keys, + src_keys_cap); a dst array that is
+ * the same pointer as the matching src array.  count and dst_cap: up to
+ * 2^32 - 1.  Asynchronous on `stream`, with no host wait.  `work`:
+ * lzf_gpu_store_renumber_work_size(count) bytes of device scratch that must
+ * stay valid until the stream's work is done.
+ *
+ * Limits: semispace only; a short key (below 256 bytes) is staged by one lane.
+ */
+typedef struct lzf_store_items {          /* device pointers */
+    uint64_t *val_off;  uint32_t *val_size;  uint8_t *enc;  uint32_t *val_len;
+    uint64_t *key_off;  uint32_t *key_len;
+    int64_t  *item_time; int32_t *item_ttl;  /* both or neither */
+    int64_t  *item_lock;                     /* optional */
+    int64_t  *last_access;                   /* optional */
+} lzf_store_items;
+
+uint64_t lzf_gpu_store_renumber_work_size(uint32_t count);
+int lzf_gpu_store_renumber(const lzf_store_items *src, uint32_t count,
+                           const uint8_t *src_keys, uint64_t src_keys_cap,
+                           const lzf_store_items *dst, uint32_t dst_cap,
+                           uint8_t *dst_keys, uint64_t dst_keys_cap, uint64_t *dst_keys_used,
+                           uint32_t *remap /* count u32, may be NULL */,
+                           uint64_t *report /* 4 u64 */, uint32_t *status,
+                           void *work, void *stream);
+
+/* An index list made before a renumbering (a select's or a lookup's output
+ * still in flight), translated in place: idx[k] = idx[k] < count ?
+ * remap[idx[k]] : 0xFFFFFFFF, count being the renumbering's.  Duplicates are
+ * fine.  LZF_GPU_EARG: a NULL pointer, n == 0, count == 0. */
+int lzf_gpu_store_remap(uint32_t *idx, uint32_t n, const uint32_t *remap, uint32_t count, void *stream);
 
 /*
  * Prefix operators over the device store: select, MGET, COUNT, MTTL.
@@ -866,10 +949,13 @@ int lzf_gpu_store_keys(const uint32_t *idx, uint32_t n,
  * LZF_ENC_NULL) keeps its place and a later insert of the same key takes it
  * over.
  *
- * Rebuild: clear the table and *used, then insert [0, count).  Dead items
- * drop out and *used becomes the number of distinct live keys.  It belongs
- * with lzf_gpu_store_compact: both are the store's housekeeping, run when
- * lzf_gpu_store_usage shows enough dead items, and item indices survive both.
+ * Rebuild: clear the table and *used, then insert [0, count) --
+ * lzf_gpu_key_index_rebuild does all of it on the stream.  Dead items drop out
+ * and *used becomes the number of distinct live keys.  It belongs with
+ * lzf_gpu_store_compact and lzf_gpu_store_renumber, the store's housekeeping,
+ * run when lzf_gpu_store_usage shows enough dead items.  Item indices survive
+ * a compaction and a rebuild; after a renumbering the table names old indices
+ * and must be rebuilt over the new arrays before the next lookup.
  *
  * Locks: SET on a locked item replies REPL_ERR_LOCKED (src/query.c:446-451);
  * lzf_gpu_store_set_guard, run between the lookup of a batch's own keys and
@@ -921,6 +1007,27 @@ int lzf_gpu_key_index_insert(void *table, uint32_t slots, uint32_t *used,
                              const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
                              uint8_t *enc, uint32_t count, uint32_t first, uint32_t n,
                              uint64_t *result /* 4 u64 */, uint32_t *status, void *stream);
+
+/*
+ * Rebuild: the table and *used are cleared on the stream, then every item of
+ * [0, count) is inserted, as lzf_gpu_key_index_insert(first = 0, n = count)
+ * into an empty table does -- with one difference.  LZF_KIDX_FULL is judged on
+ * the number of items the insert will not skip (live and key_len > 0), counted
+ * on the device, not on count: it is FULL exactly when that number exceeds
+ * slots - slots / 4.  So count = dst_cap after a lzf_gpu_store_renumber whose
+ * `live` the host has not read yet is not refused for its dead tail.  On FULL
+ * the table stays cleared, *used is 0, result is zero and no enc changes.
+ * Otherwise result and the superseding of duplicate live keys are the
+ * insert's: the highest index wins, which after a renumbering (stable) is the
+ * winner from before it.  result[0] serves as the counting word before the
+ * decision; there is no work area.  LZF_GPU_EARG, before any HIP call: a NULL
+ * pointer, count == 0, a bad `slots`, a table that is not 8-byte aligned.
+ * Asynchronous on `stream`, with no host wait.
+ */
+int lzf_gpu_key_index_rebuild(void *table, uint32_t slots, uint32_t *used,
+                              const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                              uint8_t *enc, uint32_t count,
+                              uint64_t *result /* 4 u64 */, uint32_t *status, void *stream);
 
 /*
  * Lookup of nq query keys (qkeys / q_off / q_len, an arena of their own or
