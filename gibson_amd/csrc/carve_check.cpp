@@ -130,6 +130,15 @@ int main()
             fill("renumber.w_tile_d", a.w_tile_d, nt);
             settle("renumber", n);
         });
+        at_every_misalignment(lzf_append_work_bytes(n), [&](void *work) {
+            LzfAppendArgs a{};
+            a.n = n;
+            lzf_append_carve(a, work);
+            fill("append.w_state", a.w_state, SD_STATE_WORDS);
+            fill("append.w_tile_n", a.w_tile_n, nt);
+            fill("append.w_tile_b", a.w_tile_b, nt);
+            settle("append", n);
+        });
         at_every_misalignment(lzf_select_work_bytes(n), [&](void *work) {
             LzfSelectArgs a{};
             a.count = n;

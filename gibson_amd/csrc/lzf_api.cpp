@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "lzf_internal.h"
+#include "lzf_request.h"
 #include "../../include/lzf.h"
 #include "../../include/lzf_gpu.h"
 
@@ -1035,6 +1036,84 @@ int lzf_gpu_store_replies(const uint32_t *idx, uint32_t n, int mode, const uint8
 int lzf_host_reply_code(int ent_status)
 {
     return lzf_reply_code(ent_status);
+}
+
+/* the arguments of both request parses; false: LZF_GPU_EARG */
+static bool request_args(LzfRequestArgs &a, const uint8_t *req, uint64_t req_bytes, const uint64_t *req_off,
+                         const uint32_t *req_len, uint32_t n, uint32_t max_key, uint32_t max_value, uint32_t expect_op,
+                         uint8_t *op, uint8_t *status, uint64_t *key_off, uint32_t *key_len, uint64_t *val_off,
+                         uint32_t *val_len, int64_t *num, uint64_t *result)
+{
+    if (!req || !req_off || !req_len || !op || !status || !key_off || !key_len || !val_off || !val_len || !num ||
+        !result)
+        return false;
+    if (!n || !max_key || !max_value) return false;
+    a = LzfRequestArgs{req, req_bytes, req_off, req_len, n, max_key, max_value, expect_op,
+                       op, status, key_off, val_off, key_len, val_len, num, result};
+    return true;
+}
+
+int lzf_gpu_request_parse(const uint8_t *req, uint64_t req_bytes, const uint64_t *req_off, const uint32_t *req_len,
+                          uint32_t n, uint32_t max_key, uint32_t max_value, uint32_t expect_op,
+                          uint8_t *op, uint8_t *status, uint64_t *key_off, uint32_t *key_len,
+                          uint64_t *val_off, uint32_t *val_len, int64_t *num, uint64_t *result, void *stream)
+{
+    LzfRequestArgs a{};
+    if (!request_args(a, req, req_bytes, req_off, req_len, n, max_key, max_value, expect_op, op, status, key_off,
+                      key_len, val_off, val_len, num, result))
+        return LZF_GPU_EARG;
+    if (const int rc = current_device_ok()) return rc;
+    return rc_of(lzf_launch_request_parse(a, (hipStream_t)stream));
+}
+
+int lzf_host_request_parse(const uint8_t *req, uint64_t req_bytes, const uint64_t *req_off, const uint32_t *req_len,
+                           uint32_t n, uint32_t max_key, uint32_t max_value, uint32_t expect_op,
+                           uint8_t *op, uint8_t *status, uint64_t *key_off, uint32_t *key_len,
+                           uint64_t *val_off, uint32_t *val_len, int64_t *num, uint64_t *result)
+{
+    LzfRequestArgs a{};
+    if (!request_args(a, req, req_bytes, req_off, req_len, n, max_key, max_value, expect_op, op, status, key_off,
+                      key_len, val_off, val_len, num, result))
+        return LZF_GPU_EARG;
+    for (uint32_t c = 0; c < LZF_REQ_NSTATUS; c++) result[c] = 0ull;
+    for (uint32_t k = 0; k < n; k++) result[lzf_request_entry(a, k)]++;
+    return LZF_GPU_OK;
+}
+
+int lzf_host_request_reply_code(int status)
+{
+    return lzf_request_reply_code_of(status);
+}
+
+uint64_t lzf_gpu_store_append_keys_work_size(uint32_t n)
+{
+    return lzf_append_work_bytes(n);
+}
+
+int lzf_gpu_store_append_keys(const uint8_t *req, uint64_t req_bytes, const uint8_t *op, const uint8_t *status,
+                              const uint64_t *rq_key_off, const uint32_t *rq_key_len, const uint32_t *rq_val_len,
+                              const int64_t *num, uint32_t n, uint8_t *keys, uint64_t keys_cap, uint64_t *keys_used,
+                              uint64_t *key_off, uint32_t *key_len, int64_t *item_time, int32_t *item_ttl,
+                              int64_t *item_lock, int64_t *last_access, uint32_t first, uint32_t count, int64_t now,
+                              int32_t max_item_ttl, uint32_t *set_len, uint32_t *void_idx, uint64_t *result,
+                              void *work, void *stream)
+{
+    if (!req || !op || !status || !rq_key_off || !rq_key_len || !rq_val_len || !num || !keys || !keys_used ||
+        !key_off || !key_len || !set_len || !void_idx || !result || !work)
+        return LZF_GPU_EARG;
+    if (!n || !count || !keys_cap || (uint64_t)first + n > count || !item_time != !item_ttl) return LZF_GPU_EARG;
+    if (const int rc = current_device_ok()) return rc;
+    LzfAppendArgs a{};
+    a.req = req; a.req_bytes = req_bytes; a.op = op; a.status = status;
+    a.rq_key_off = rq_key_off; a.rq_key_len = rq_key_len; a.rq_val_len = rq_val_len; a.num = num;
+    a.n = n; a.first = first;
+    a.keys = keys; a.keys_cap = keys_cap; a.keys_used = keys_used;
+    a.key_off = key_off; a.key_len = key_len;
+    a.item_time = item_time; a.item_ttl = item_ttl; a.item_lock = item_lock; a.last_access = last_access;
+    a.now = now; a.max_item_ttl = max_item_ttl;
+    a.set_len = set_len; a.void_idx = void_idx; a.result = result;
+    lzf_append_carve(a, work);
+    return rc_of(lzf_launch_store_append_keys(a, (hipStream_t)stream));
 }
 
 int lzf_gpu_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,

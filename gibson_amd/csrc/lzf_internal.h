@@ -152,6 +152,35 @@ struct LzfRenumberArgs {
     uint64_t *w_state, *w_tile_n, *w_tile_b, *w_tile_d;
 };
 
+/* the key append of a parsed SET batch (lzf_request.hip); device pointers.
+ * The rq_* arrays are the parse's outputs, n entries; key_off .. last_access
+ * the store's, `count` entries, written at [first, first + n) */
+struct LzfAppendArgs {
+    const uint8_t *req;
+    uint64_t req_bytes;
+    const uint8_t *op, *status;
+    const uint64_t *rq_key_off;
+    const uint32_t *rq_key_len, *rq_val_len;
+    const int64_t *num;
+    uint32_t n, first;
+    uint8_t *keys;
+    uint64_t keys_cap;
+    uint64_t *keys_used;
+    uint64_t *key_off;
+    uint32_t *key_len;
+    int64_t *item_time;
+    int32_t *item_ttl;
+    int64_t *item_lock, *last_access;
+    int64_t now;
+    int32_t max_item_ttl;
+    uint32_t *set_len, *void_idx;
+    uint64_t *result;
+    /* work area (lzf_append_layout): per scan tile the accepted count and the
+     * accepted key bytes; after the carry the latter holds the sum of the tiles
+     * before */
+    uint64_t *w_state, *w_tile_n, *w_tile_b;
+};
+
 /* the prefix select over the store's keys (lzf_mget.hip); device pointers */
 struct LzfSelectArgs {
     const uint8_t *keys;
@@ -418,6 +447,13 @@ hipError_t lzf_launch_store_renumber(LzfRenumberArgs &a, hipStream_t s);
 hipError_t lzf_launch_store_remap(uint32_t *idx, uint32_t n, const uint32_t *remap, uint32_t count, hipStream_t s);
 uint64_t lzf_renumber_work_bytes(uint32_t count);
 void lzf_renumber_carve(LzfRenumberArgs &a, void *work);
+/* request ingest (lzf_request.hip): the parse of a batch of raw requests (the
+ * grammar: lzf_request.h), and the key append of a parsed SET batch */
+struct LzfRequestArgs;
+hipError_t lzf_launch_request_parse(const LzfRequestArgs &a, hipStream_t s);
+hipError_t lzf_launch_store_append_keys(LzfAppendArgs &a, hipStream_t s);
+uint64_t lzf_append_work_bytes(uint32_t n);
+void lzf_append_carve(LzfAppendArgs &a, void *work);
 /* the operators over the store (lzf_mget.hip): the prefix select into an
  * index list, and MGET (`decode` over the gathered entries, in place in the
  * frame), COUNT and MTTL over an index list */

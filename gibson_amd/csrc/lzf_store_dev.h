@@ -1,8 +1,9 @@
 /*
  * lzf_store_dev.h -- the toolkit of the device store's kernels (lzf_frame.hip,
  * lzf_store.hip, lzf_mget.hip, lzf_kidx.hip, lzf_ops.hip, lzf_mset.hip,
- * lzf_meta.hip, lzf_reply.hip, lzf_renumber.hip), over the byte helpers of lzf_dev.h and the
- * geometry of lzf_store_layout.h.  One copy of each: the pad and the "no
+ * lzf_meta.hip, lzf_reply.hip, lzf_renumber.hip, lzf_request.hip), over the byte helpers of
+ * lzf_dev.h, the geometry of lzf_store_layout.h and the request grammar of
+ * lzf_request.h, where the number parse lives.  One copy of each: the pad and the "no
  * entry" class; the ballot count, the 64-bit wave sum and the wave leader's
  * add; the block scan and the carry scan over tile sums; put32, the reply
  * header, the wave copy and the decode batch; and the per-item rules over the
@@ -16,6 +17,7 @@
 
 #include "lzf_dev.h"
 #include "lzf_store_layout.h"
+#include "lzf_request.h"
 
 #define SD_PAD  0xFFFFFFFFu               /* an index-list entry that names no item */
 #define SD_NONE 0xFFu                     /* no entry: the class of a lane past the list's end */
@@ -229,29 +231,8 @@ __device__ inline uint32_t sd_entry_class(uint32_t i, const LzfItems &it, bool e
     return v == MG_EXPIRED ? LZF_ENT_EXPIRED : LZF_ENT_DONE;
 }
 
-/* gbQueryParseLong (src/query.c:39-76), quirk for quirk: a first byte '0'
- * yields 0 whatever follows; a leading '-' negates and a lone "-" is 0; every
- * other byte must be a digit; no length limit, the accumulation n * 10 + d and
- * the negation modulo 2^64 (what the reference's x86-64 build computes where C
- * leaves the signed overflow undefined).  len == 0: not a number (the
- * reference asserts vlen > 0) */
-__host__ __device__ inline int lzf_parse_long(const uint8_t *v, uint32_t len, int64_t *out)
-{
-    if (!len) return 0;
-    if (v[0] == (uint8_t)'0') {
-        *out = 0;
-        return 1;
-    }
-    const uint32_t neg = v[0] == (uint8_t)'-' ? 1u : 0u;
-    uint64_t n = 0ull;
-    for (uint32_t i = neg; i < len; i++) {
-        const uint32_t d = (uint32_t)v[i] - (uint32_t)'0';
-        if (d > 9u) return 0;
-        n = n * 10ull + d;
-    }
-    *out = (int64_t)(neg ? 0ull - n : n);
-    return 1;
-}
+/* the number parse, gbQueryParseLong: lzf_parse_long of lzf_request.h, beside
+ * the request grammar that needs it on the host too */
 
 /* The reply code of an operator's entry status, the single-key replies of
  * gbQueryIncDecHandler and its kin (src/query.c:853-886): REPL_VAL for an

@@ -146,6 +146,16 @@ static inline void lzf_renumber_layout(LzfRenumberArgs &a, LzfCarver &c)
     a.w_tile_d = c.take<uint64_t>(nt);
 }
 
+/* append_keys (lzf_request.hip): per-tile sums only, as the renumbering */
+static inline void lzf_append_layout(LzfAppendArgs &a, LzfCarver &c)
+{
+    const uint64_t nt = sd_tiles(a.n);
+    c.align(8);
+    a.w_state = c.take<uint64_t>(SD_STATE_WORDS);
+    a.w_tile_n = c.take<uint64_t>(nt);
+    a.w_tile_b = c.take<uint64_t>(nt);
+}
+
 /* select (lzf_mget.hip) */
 static inline void lzf_select_layout(LzfSelectArgs &a, LzfCarver &c)
 {

@@ -88,6 +88,11 @@ EXPORTS = (
     "lzf_gpu_store_renumber",
     "lzf_gpu_store_remap",
     "lzf_gpu_key_index_rebuild",
+    "lzf_gpu_request_parse",
+    "lzf_host_request_parse",
+    "lzf_host_request_reply_code",
+    "lzf_gpu_store_append_keys_work_size",
+    "lzf_gpu_store_append_keys",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -120,6 +125,12 @@ ENC_PLAIN, ENC_LZF, ENC_NUMBER, ENC_NULL = 0x00, 0x01, 0x02, 0xFF
 REPL_KVAL = 7
 # the reply codes of store_replies (src/query.h:64-70)
 REPL_ERR, REPL_ERR_NOT_FOUND, REPL_ERR_NAN, REPL_ERR_LOCKED, REPL_OK, REPL_VAL = 0, 1, 2, 4, 5, 6
+# the opcodes of a request (src/query.h:37-59) and the status of request_parse
+(OP_SET, OP_TTL, OP_GET, OP_DEL, OP_INC, OP_DEC, OP_LOCK, OP_UNLOCK, OP_MSET, OP_MTTL, OP_MGET, OP_MDEL, OP_MINC,
+ OP_MDEC, OP_MLOCK, OP_MUNLOCK, OP_COUNT, OP_STATS, OP_PING, OP_META, OP_KEYS) = range(1, 22)
+OP_END = 0xFF
+REQ_OK, REQ_ERR, REQ_NAN, REQ_BADOP, REQ_SHORT, REQ_ERANGE, REQ_OTHER = 0, 1, 2, 3, 4, 5, 6
+REQ_NSTATUS = 7
 
 
 class LzfLibraryMissing(ImportError):
@@ -237,6 +248,8 @@ def _load(path):
         _bind_store_replies(L)
     if hasattr(L, "lzf_gpu_store_renumber"):
         _bind_store_renumber(L)
+    if hasattr(L, "lzf_gpu_request_parse"):
+        _bind_request(L)
     del i32
     _LOADED[path] = L
     return L
@@ -318,6 +331,24 @@ def _bind_store_renumber(L):
     L.lzf_gpu_store_remap.argtypes = [vp, u32, vp, u32, vp]
     L.lzf_gpu_key_index_rebuild.restype = ctypes.c_int
     L.lzf_gpu_key_index_rebuild.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
+
+
+def _bind_request(L):
+    """Request ingest: the parse of raw requests and the key append of a SET
+    batch; absent from an older build given by LZF_HIP_LIB (the helpers below
+    then raise AttributeError)."""
+    u32, u64, vp, i64, i32 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    L.lzf_gpu_request_parse.restype = ctypes.c_int
+    L.lzf_gpu_request_parse.argtypes = [vp, u64, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lzf_host_request_parse.restype = ctypes.c_int
+    L.lzf_host_request_parse.argtypes = [vp, u64, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lzf_host_request_reply_code.restype = ctypes.c_int
+    L.lzf_host_request_reply_code.argtypes = [ctypes.c_int]
+    L.lzf_gpu_store_append_keys_work_size.restype = u64
+    L.lzf_gpu_store_append_keys_work_size.argtypes = [u32]
+    L.lzf_gpu_store_append_keys.restype = ctypes.c_int
+    L.lzf_gpu_store_append_keys.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp,
+                                            u32, u32, i64, i32, vp, vp, vp, vp, vp]
 
 
 def _bind_store_index(L):
@@ -1080,6 +1111,107 @@ def store_set_guard(occ, first, enc, item_time, item_lock, now, result, refused=
     _check(lib().lzf_gpu_store_set_guard(_ptr(occ), int(first), int(occ.numel()), _ptr(enc), int(enc.numel()),
                                          _ptr(item_time), _ptr(item_lock), int(now), _opt_ptr(refused), _ptr(result),
                                          _stream_handle(stream)), "lzf_gpu_store_set_guard")
+
+
+# ---- request ingest: raw requests in, descriptors out ------------------------------
+
+class ParsedRequests:
+    """The seven output arrays of request_parse, n entries each: op and status
+    uint8, key_off / val_off int64 (absolute into the request arena), key_len /
+    val_len int32, num int64.  Tensors on one device, or numpy arrays from
+    host_request_parse."""
+    FIELDS = ("op", "status", "key_off", "key_len", "val_off", "val_len", "num")
+
+    def __init__(self, op, status, key_off, key_len, val_off, val_len, num):
+        self.op, self.status, self.key_off, self.key_len = op, status, key_off, key_len
+        self.val_off, self.val_len, self.num = val_off, val_len, num
+
+    @classmethod
+    def empty(cls, n, device):
+        import torch
+        dt = {"op": torch.uint8, "status": torch.uint8, "key_len": torch.int32, "val_len": torch.int32}
+        return cls(*(torch.empty(n, dtype=dt.get(f, torch.int64), device=device) for f in cls.FIELDS))
+
+
+def request_parse(req, req_off, req_len, max_key, max_value, out, result, expect_op=0, stream=None):
+    """The reference's request grammar over a batch: request k is
+    ``req[req_off[k] : req_off[k] + req_len[k]]`` (req uint8, req_off int64,
+    req_len int32 read as u32), ``[i16 opcode][payload]``.  ``out`` (a
+    ParsedRequests) receives the opcode, a REQ_* status, the key and value
+    spans with offsets absolute into ``req`` and the number; result
+    (REQ_NSTATUS elements, int64) how many requests got each status.  With
+    ``expect_op`` every other opcode is REQ_OTHER.  No byte outside ``req`` is
+    read.  No host wait."""
+    rc = lib().lzf_gpu_request_parse(_ptr(req), int(req.numel()), _ptr(req_off), _ptr(req_len), int(req_len.numel()),
+                                     int(max_key), int(max_value), int(expect_op), _ptr(out.op), _ptr(out.status),
+                                     _ptr(out.key_off), _ptr(out.key_len), _ptr(out.val_off), _ptr(out.val_len),
+                                     _ptr(out.num), _ptr(result), _stream_handle(stream))
+    _check(rc, "lzf_gpu_request_parse")
+    return out
+
+
+def host_request_parse(req, req_off, req_len, max_key, max_value, expect_op=0):
+    """request_parse on the host over numpy arrays (req uint8, req_off uint64,
+    req_len uint32), the same function in a loop: (ParsedRequests of numpy
+    arrays, result as a numpy uint64 array).  No GPU."""
+    import numpy as np
+    req = np.ascontiguousarray(req, dtype=np.uint8)
+    req_off = np.ascontiguousarray(req_off, dtype=np.uint64)
+    req_len = np.ascontiguousarray(req_len, dtype=np.uint32)
+    n = len(req_len)
+    dt = {"op": np.uint8, "status": np.uint8, "key_off": np.uint64, "key_len": np.uint32, "val_off": np.uint64,
+          "val_len": np.uint32, "num": np.int64}
+    out = ParsedRequests(*(np.zeros(n, dtype=dt[f]) for f in ParsedRequests.FIELDS))
+    result = np.zeros(REQ_NSTATUS, dtype=np.uint64)
+    base = ctypes.c_void_p(req.ctypes.data if len(req) else ctypes.addressof(ctypes.create_string_buffer(1)))
+    rc = lib().lzf_host_request_parse(base, len(req), _np_ptr(req_off), _np_ptr(req_len), n, int(max_key),
+                                      int(max_value), int(expect_op), _np_ptr(out.op), _np_ptr(out.status),
+                                      _np_ptr(out.key_off), _np_ptr(out.key_len), _np_ptr(out.val_off),
+                                      _np_ptr(out.val_len), _np_ptr(out.num), _np_ptr(result))
+    _check(rc, "lzf_host_request_parse")
+    return out, result
+
+
+def request_reply_code(status):
+    """lzf_host_request_reply_code: -1 for REQ_OK (the operator replies), -2
+    for REQ_BADOP (close the connection), REPL_ERR_NAN for REQ_NAN, REPL_ERR
+    otherwise.  No device call."""
+    return int(lib().lzf_host_request_reply_code(int(status)))
+
+
+def store_append_keys_work(n, device):
+    """A scratch tensor for one store_append_keys call over ``n`` requests."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_store_append_keys_work_size(int(n))), dtype=torch.uint8, device=device)
+
+
+def store_append_keys(req, parsed, keys, keys_used, key_off, key_len, first, now, max_item_ttl, set_len, void_idx,
+                      result, item_time=None, item_ttl=None, item_lock=None, last_access=None, work=None, stream=None):
+    """SET's other half, after request_parse left ``parsed`` over ``req``: item
+    ``first + k`` belongs to request k.  An accepted request (OP_SET, REQ_OK,
+    its key inside ``req``) has its key appended to ``keys`` from
+    ``keys_used[0]`` on, which is advanced, key_off / key_len of its item
+    written, item_time = last_access = now, item_lock = 0, item_ttl = num > 0 ?
+    min(max_item_ttl, num) : -1, set_len[k] = its value's length and
+    void_idx[k] = -1; a refused one gets key_len 0, set_len 0 and void_idx[k] =
+    first + k, for store_delete after set_store.  key_off .. last_access are
+    the store's arrays (count = key_len's length); set_len and void_idx int32,
+    one per request; result (4 elements, int64) = accepted, refused, key bytes,
+    STORE_OK or STORE_FULL (the call refused whole, nothing appended).  No host
+    wait; returns ``work`` (store_append_keys_work), which must outlive the
+    stream's work."""
+    n = parsed.status.numel()
+    if work is None:
+        work = store_append_keys_work(n, keys.device)
+    rc = lib().lzf_gpu_store_append_keys(_ptr(req), int(req.numel()), _ptr(parsed.op), _ptr(parsed.status),
+                                         _ptr(parsed.key_off), _ptr(parsed.key_len), _ptr(parsed.val_len),
+                                         _ptr(parsed.num), n, _ptr(keys), int(keys.numel()), _ptr(keys_used),
+                                         _ptr(key_off), _ptr(key_len), _opt_ptr(item_time), _opt_ptr(item_ttl),
+                                         _opt_ptr(item_lock), _opt_ptr(last_access), int(first), int(key_len.numel()),
+                                         int(now), int(max_item_ttl), _ptr(set_len), _ptr(void_idx), _ptr(result),
+                                         _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_append_keys")
+    return work
 
 
 # ---- MSET by prefix, the memory sweep, META and the KEYS frame --------------------

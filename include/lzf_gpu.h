@@ -1155,6 +1155,171 @@ int lzf_gpu_store_replies(const uint32_t *idx, uint32_t n, int mode,
 /* host, no HIP call: the LZF_REPL_* code of an LZF_ENT_* entry status */
 int lzf_host_reply_code(int ent_status);
 
+/*
+ * Request ingest: raw request buffers in, the descriptors of every call above
+ * out, without the host reading a request.
+ *
+ * A request is what gbProcessQuery sees (src/query.c:1393-1485): client->buffer
+ * of buffer_size bytes, [i16 opcode, little-endian][payload], size =
+ * buffer_size - 2; the wire's 4-byte length prefix is not part of it.  Request
+ * k of a batch is req[req_off[k] .. + req_len[k]) in one arena of req_bytes
+ * bytes.  The parse is the reference's, quirk for quirk (src/query.c:229-373):
+ *
+ *   grammar                       operators                         num
+ *   key only                      GET DEL INC DEC UNLOCK MDEL MINC  -
+ *                                 MDEC MUNLOCK COUNT KEYS
+ *   key and required value        MSET (the value), META (a field)  -
+ *   key and required number       TTL MTTL LOCK MLOCK               lzf_host_parse_long of the value
+ *   key and optional number       MGET                              the limit, -1 without a value
+ *   ttl, key, value               SET                               the raw ttl (:444)
+ *   no payload read               STATS PING END                    -
+ *
+ * The key scan stops at the first ' ' or after end = min(size, max_key) bytes;
+ * SET's ttl token and key share one budget of end (:334-347); one byte is
+ * skipped after each token, space or not; the value is size - ttllen - klen -
+ * 2 bytes (SET), size - klen - 1 (key and value) or left - 1 (MGET), clamped
+ * to max_value; the checks run in the order ttl token, key, value.
+ *
+ * status[k] is one of LZF_REQ_*.  LZF_REQ_SHORT is the one deliberate
+ * departure from the reference: where the payload ends with the key ("10 key"
+ * for SET, "abc" for TTL, a key of exactly max_key bytes with nothing behind
+ * it) the reference's unsigned subtraction wraps, min() makes it maxvaluesize
+ * and the handler reads past its buffer; here the request is refused and the
+ * reply is REPL_ERR.  Every status but OK and NAN leaves the spans and num 0;
+ * NAN keeps its spans, because the single-key TTL and LOCK handlers look the
+ * key up before they test the number (:553-565, :983-985): the caller needs
+ * the key to choose between REPL_ERR_NOT_FOUND and REPL_ERR_NAN.
+ *
+ * Outputs, n entries each: op (u8: 1-21, 0xFF, or 0 for BADOP and ERANGE),
+ * status (u8), key_off (u64) / key_len (u32), val_off (u64) / val_len (u32),
+ * num (i64).  The offsets are absolute into req (0 with a length of 0), so the
+ * outputs feed the calls above as they are: for lzf_gpu_set_store req is `in`,
+ * val_off is in_off and lzf_gpu_store_append_keys' set_len is in_len; for
+ * lzf_gpu_key_index_lookup req is qkeys and key_off / key_len are q_off /
+ * q_len.  A key_len of 0 is a miss in the lookup, so a refused request is
+ * padding for every index-list operator.  With expect_op != 0 a request with
+ * any other (known) opcode gets LZF_REQ_OTHER and zero spans.  result
+ * (LZF_REQ_NSTATUS device u64): how many requests got each status.
+ *
+ * No byte outside [req, req + req_bytes) is read and no output depends on a
+ * byte outside the request's own range.  LZF_GPU_EARG, before any HIP call: a
+ * NULL pointer, n == 0, max_key == 0, max_value == 0.  Asynchronous on
+ * `stream`, with no host wait.  lzf_host_request_parse is the same function in
+ * a host loop over host arrays, with no HIP call.
+ */
+#define LZF_OP_SET      1    /* src/query.h:37-59 */
+#define LZF_OP_TTL      2
+#define LZF_OP_GET      3
+#define LZF_OP_DEL      4
+#define LZF_OP_INC      5
+#define LZF_OP_DEC      6
+#define LZF_OP_LOCK     7
+#define LZF_OP_UNLOCK   8
+#define LZF_OP_MSET     9
+#define LZF_OP_MTTL     10
+#define LZF_OP_MGET     11
+#define LZF_OP_MDEL     12
+#define LZF_OP_MINC     13
+#define LZF_OP_MDEC     14
+#define LZF_OP_MLOCK    15
+#define LZF_OP_MUNLOCK  16
+#define LZF_OP_COUNT    17
+#define LZF_OP_STATS    18
+#define LZF_OP_PING     19
+#define LZF_OP_META     20
+#define LZF_OP_KEYS     21
+#define LZF_OP_END      0xFF
+
+#define LZF_REQ_OK       0   /* parsed */
+#define LZF_REQ_ERR      1   /* the parse function returns 0 (REPL_ERR); SET with size 0 */
+#define LZF_REQ_NAN      2   /* the number does not parse (REPL_ERR_NAN); the spans are kept */
+#define LZF_REQ_BADOP    3   /* no branch in gbProcessQuery, or shorter than 2 bytes: GB_ERR, drop the client */
+#define LZF_REQ_SHORT    4   /* the value span would leave the request (the reference over-reads) */
+#define LZF_REQ_ERANGE   5   /* req_off + req_len > req_bytes */
+#define LZF_REQ_OTHER    6   /* a known opcode, but not expect_op */
+#define LZF_REQ_NSTATUS  7
+
+int lzf_gpu_request_parse(const uint8_t *req, uint64_t req_bytes,
+                          const uint64_t *req_off, const uint32_t *req_len, uint32_t n,
+                          uint32_t max_key, uint32_t max_value, uint32_t expect_op,
+                          uint8_t *op, uint8_t *status, uint64_t *key_off, uint32_t *key_len,
+                          uint64_t *val_off, uint32_t *val_len, int64_t *num,
+                          uint64_t *result /* LZF_REQ_NSTATUS u64 */, void *stream);
+int lzf_host_request_parse(const uint8_t *req, uint64_t req_bytes,
+                           const uint64_t *req_off, const uint32_t *req_len, uint32_t n,
+                           uint32_t max_key, uint32_t max_value, uint32_t expect_op,
+                           uint8_t *op, uint8_t *status, uint64_t *key_off, uint32_t *key_len,
+                           uint64_t *val_off, uint32_t *val_len, int64_t *num,
+                           uint64_t *result /* LZF_REQ_NSTATUS u64 */);
+/* host, no HIP call: -1 for LZF_REQ_OK (the operator replies), -2 for
+ * LZF_REQ_BADOP (close the connection), LZF_REPL_ERR_NAN for LZF_REQ_NAN,
+ * LZF_REPL_ERR otherwise */
+int lzf_host_request_reply_code(int status);
+
+/*
+ * SET's other half: the keys of a parsed SET batch appended to the store's key
+ * arena and the new items' key and time members filled, so that
+ * lzf_gpu_set_store can follow without the host knowing a key.
+ *
+ * The call serves the n requests of a batch as lzf_gpu_request_parse left
+ * them (op, status, rq_key_off, rq_key_len, rq_val_len, num; req / req_bytes
+ * the same arena).  Item first + k belongs to request k, accepted or not, so
+ * the caller needs no count from the device.  Request k is accepted iff
+ * op[k] == LZF_OP_SET, status[k] == LZF_REQ_OK and [rq_key_off[k], +
+ * rq_key_len[k]) lies inside [0, req_bytes) (64-bit, wrap-safe); otherwise it
+ * is refused.
+ *
+ * Accepted: the key bytes are appended to `keys`, dense and in request order,
+ * from base = *keys_used; key_off[first + k] = base + the accepted key bytes
+ * before k, key_len[first + k] = rq_key_len[k]; item_time = last_access = now,
+ * item_lock = 0, item_ttl = num > 0 ? min(max_item_ttl, num) : -1
+ * (gbCreateItem at src/query.c:113-128, then :454-458); set_len[k] =
+ * rq_val_len[k]; void_idx[k] = 0xFFFFFFFF.
+ * Refused: key_len = 0 and key_off the running end offset (the tie that
+ * renumbering's tail leaves); the time members as for a fresh item without a
+ * TTL (item_ttl -1); set_len[k] = 0; void_idx[k] = first + k.  After
+ * lzf_gpu_set_store(in = req, in_off = val_off, in_len = set_len) has run,
+ * lzf_gpu_store_delete(void_idx, n, ...) nulls the refused requests' items: a
+ * refused request costs zero bytes and one burnt index.
+ *
+ * result (4 device u64): [0] accepted, [1] refused, [2] key bytes appended,
+ * [3] LZF_STORE_OK or LZF_STORE_FULL.  FULL -- base + the accepted key bytes
+ * exceed keys_cap or wrap -- is decided before any byte is written and refuses
+ * the call whole: no byte of `keys` is written, *keys_used is unchanged, every
+ * request is refused as above (set_len 0, void_idx first + k, key_len 0), and
+ * result is [0, n, 0, LZF_STORE_FULL].  On OK *keys_used = base + result[2].
+ *
+ * item_time and item_ttl: both or neither; item_lock and last_access may be
+ * NULL.  LZF_GPU_EARG, before any HIP call: a NULL pointer but those, n == 0,
+ * count == 0, keys_cap == 0, first + n > count (64-bit), exactly one of
+ * item_time / item_ttl.  `work`: lzf_gpu_store_append_keys_work_size(n) bytes
+ * of device scratch that must stay valid until the stream's work is done.
+ * Asynchronous on `stream`, with no host wait.
+ *
+ * One SET batch on one stream: lzf_gpu_request_parse ->
+ * lzf_gpu_store_append_keys -> lzf_gpu_set_store -> lzf_gpu_store_delete(
+ * void_idx) -> lzf_gpu_key_index_lookup of the new items' own keys ->
+ * lzf_gpu_store_set_guard -> lzf_gpu_store_replies(LZF_REPLY_GET) over first
+ * .. first + n (the SET reply, gbClientEnqueueItem(REPL_VAL, item) at :460;
+ * before the insert, so that a batch's superseded duplicates still get their
+ * own value back) -> lzf_gpu_key_index_insert.  The host overrides the reply
+ * of a refused request from `status` and of a locked key from `refused`.
+ *
+ * Limits: a short key (below 256 bytes) is staged by one lane.
+ */
+uint64_t lzf_gpu_store_append_keys_work_size(uint32_t n);
+int lzf_gpu_store_append_keys(const uint8_t *req, uint64_t req_bytes,
+                              const uint8_t *op, const uint8_t *status,
+                              const uint64_t *rq_key_off, const uint32_t *rq_key_len,
+                              const uint32_t *rq_val_len, const int64_t *num, uint32_t n,
+                              uint8_t *keys, uint64_t keys_cap, uint64_t *keys_used,
+                              uint64_t *key_off, uint32_t *key_len,
+                              int64_t *item_time, int32_t *item_ttl,
+                              int64_t *item_lock /* may be NULL */, int64_t *last_access /* may be NULL */,
+                              uint32_t first, uint32_t count, int64_t now, int32_t max_item_ttl,
+                              uint32_t *set_len /* n */, uint32_t *void_idx /* n */,
+                              uint64_t *result /* 4 u64 */, void *work, void *stream);
+
 /* Free the library's device scratch (all devices), the calling thread's and
  * the device workers' staging buffers; later calls allocate them again.
  * Each thread's staging buffers are also freed when the thread exits. */
