@@ -30,6 +30,8 @@ struct Span {
 
 static Span g_span[32];
 static unsigned g_nspan;
+static const char *g_layout[32];          /* the layouts settled so far, each name once */
+static unsigned g_nlayout;
 
 template <typename T>
 static void fill(const char *what, T *p, uint64_t count)
@@ -56,6 +58,9 @@ static void settle(const char *what, uint64_t n)
                 j = g_span[k].bytes - 1u;
             }
     g_nspan = 0;
+    for (unsigned k = 0; k < g_nlayout; k++)
+        if (!strcmp(g_layout[k], what)) return;
+    g_layout[g_nlayout++] = what;
 }
 
 /* run `use` on a buffer of exactly `size` bytes at every misalignment */
@@ -138,6 +143,13 @@ int main()
             fill("append.w_tile_n", a.w_tile_n, nt);
             fill("append.w_tile_b", a.w_tile_b, nt);
             settle("append", n);
+        });
+        at_every_misalignment(lzf_bucket_work_bytes(n), [&](void *work) {
+            LzfBucketArgs a{};
+            a.n = n;
+            lzf_bucket_carve(a, work);
+            fill("bucket.w_table", a.w_table, (uint64_t)LZF_RQ_NCLASS * nt);
+            settle("bucket", n);
         });
         at_every_misalignment(lzf_select_work_bytes(n), [&](void *work) {
             LzfSelectArgs a{};
@@ -228,6 +240,8 @@ int main()
         });
     }
     if (g_bad) return 1;
-    printf("carve_check: ok, %u arrays written\n", g_arrays);
+    printf("carve_check: ok, %u arrays written; layouts:", g_arrays);
+    for (unsigned k = 0; k < g_nlayout; k++) printf(" %s", g_layout[k]);
+    printf("\n");
     return 0;
 }

@@ -1116,6 +1116,119 @@ int lzf_gpu_store_append_keys(const uint8_t *req, uint64_t req_bytes, const uint
     return rc_of(lzf_launch_store_append_keys(a, (hipStream_t)stream));
 }
 
+int lzf_host_request_class(int op, int status)
+{
+    return (int)lzf_request_class_of((uint32_t)op, (uint32_t)status);
+}
+
+uint64_t lzf_gpu_request_bucket_work_size(uint32_t n)
+{
+    return lzf_bucket_work_bytes(n);
+}
+
+/* the arguments of both buckets; false: LZF_GPU_EARG */
+static bool bucket_args(LzfBucketArgs &a, const uint8_t *op, const uint8_t *status, const uint64_t *key_off,
+                        const uint32_t *key_len, const uint64_t *val_off, const uint32_t *val_len, const int64_t *num,
+                        uint32_t n, uint32_t *perm, uint32_t *slot, uint32_t *class_first, uint8_t *b_op,
+                        uint8_t *b_status, uint64_t *b_key_off, uint32_t *b_key_len, uint64_t *b_val_off,
+                        uint32_t *b_val_len, int64_t *b_num)
+{
+    if (!op || !status || !key_off || !key_len || !val_off || !val_len || !num || !perm || !slot || !class_first ||
+        !b_op || !b_status || !b_key_off || !b_key_len || !b_val_off || !b_val_len || !b_num || !n)
+        return false;
+    a.op = op; a.status = status; a.key_off = key_off; a.key_len = key_len;
+    a.val_off = val_off; a.val_len = val_len; a.num = num; a.n = n;
+    a.perm = perm; a.slot = slot; a.class_first = class_first;
+    a.b_op = b_op; a.b_status = b_status; a.b_key_off = b_key_off; a.b_key_len = b_key_len;
+    a.b_val_off = b_val_off; a.b_val_len = b_val_len; a.b_num = b_num;
+    return true;
+}
+
+int lzf_gpu_request_bucket(const uint8_t *op, const uint8_t *status, const uint64_t *key_off, const uint32_t *key_len,
+                           const uint64_t *val_off, const uint32_t *val_len, const int64_t *num, uint32_t n,
+                           uint32_t *perm, uint32_t *slot, uint32_t *class_first, uint8_t *b_op, uint8_t *b_status,
+                           uint64_t *b_key_off, uint32_t *b_key_len, uint64_t *b_val_off, uint32_t *b_val_len,
+                           int64_t *b_num, void *work, void *stream)
+{
+    LzfBucketArgs a{};
+    if (!bucket_args(a, op, status, key_off, key_len, val_off, val_len, num, n, perm, slot, class_first, b_op,
+                     b_status, b_key_off, b_key_len, b_val_off, b_val_len, b_num) ||
+        !work)
+        return LZF_GPU_EARG;
+    if (const int rc = current_device_ok()) return rc;
+    lzf_bucket_carve(a, work);
+    return rc_of(lzf_launch_request_bucket(a, (hipStream_t)stream));
+}
+
+int lzf_host_request_bucket(const uint8_t *op, const uint8_t *status, const uint64_t *key_off, const uint32_t *key_len,
+                            const uint64_t *val_off, const uint32_t *val_len, const int64_t *num, uint32_t n,
+                            uint32_t *perm, uint32_t *slot, uint32_t *class_first, uint8_t *b_op, uint8_t *b_status,
+                            uint64_t *b_key_off, uint32_t *b_key_len, uint64_t *b_val_off, uint32_t *b_val_len,
+                            int64_t *b_num)
+{
+    LzfBucketArgs a{};
+    if (!bucket_args(a, op, status, key_off, key_len, val_off, val_len, num, n, perm, slot, class_first, b_op,
+                     b_status, b_key_off, b_key_len, b_val_off, b_val_len, b_num))
+        return LZF_GPU_EARG;
+    lzf_request_bucket_host(op, status, key_off, key_len, val_off, val_len, num, n, perm, slot, class_first, b_op,
+                            b_status, b_key_off, b_key_len, b_val_off, b_val_len, b_num);
+    return LZF_GPU_OK;
+}
+
+/* the arguments of both stitches; false: LZF_GPU_EARG */
+static bool stitch_args(LzfStitchArgs &a, const uint8_t *op, const uint8_t *status, const uint32_t *slot,
+                            uint32_t n, const uint32_t *class_first, const uint8_t *class_mode,
+                            const uint64_t *class_base, const uint64_t *b_rep_off, const uint32_t *b_rep_len,
+                            const uint8_t *b_ent, const uint8_t *b_refused, uint8_t *replies, uint64_t rep_cap,
+                            uint64_t code_base, uint64_t *out_off, uint32_t *out_len, uint8_t *out_kind,
+                            uint64_t *result)
+{
+    if (!op || !status || !slot || !class_first || !class_mode || !class_base || !replies || !out_off || !out_len ||
+        !out_kind || !result || !n)
+        return false;
+    if (rep_cap < LZF_STITCH_CODES || code_base > rep_cap - LZF_STITCH_CODES) return false;
+    a.op = op; a.status = status; a.slot = slot; a.class_first = class_first; a.n = n;
+    for (uint32_t c = 0; c < (uint32_t)LZF_RQ_NCLASS; c++) {
+        if (class_mode[c] > (uint8_t)LZF_STITCH_CODE) return false;
+        if (class_mode[c] == (uint8_t)LZF_STITCH_ARENA && (!b_rep_off || !b_rep_len)) return false;
+        if (class_mode[c] == (uint8_t)LZF_STITCH_CODE && !b_ent) return false;
+        a.class_mode[c] = class_mode[c];
+        a.class_base[c] = class_base[c];
+    }
+    a.b_rep_off = b_rep_off; a.b_rep_len = b_rep_len; a.b_ent = b_ent; a.b_refused = b_refused;
+    a.replies = replies; a.rep_cap = rep_cap; a.code_base = code_base;
+    a.out_off = out_off; a.out_len = out_len; a.out_kind = out_kind; a.result = result;
+    return true;
+}
+
+int lzf_gpu_request_stitch(const uint8_t *op, const uint8_t *status, const uint32_t *slot, uint32_t n,
+                           const uint32_t *class_first, const uint8_t *class_mode, const uint64_t *class_base,
+                           const uint64_t *b_rep_off, const uint32_t *b_rep_len, const uint8_t *b_ent,
+                           const uint8_t *b_refused, uint8_t *replies, uint64_t rep_cap, uint64_t code_base,
+                           uint64_t *out_off, uint32_t *out_len, uint8_t *out_kind, uint64_t *result, void *stream)
+{
+    LzfStitchArgs a{};
+    if (!stitch_args(a, op, status, slot, n, class_first, class_mode, class_base, b_rep_off, b_rep_len, b_ent,
+                         b_refused, replies, rep_cap, code_base, out_off, out_len, out_kind, result))
+        return LZF_GPU_EARG;
+    if (const int rc = current_device_ok()) return rc;
+    return rc_of(lzf_launch_request_stitch(a, (hipStream_t)stream));
+}
+
+int lzf_host_request_stitch(const uint8_t *op, const uint8_t *status, const uint32_t *slot, uint32_t n,
+                            const uint32_t *class_first, const uint8_t *class_mode, const uint64_t *class_base,
+                            const uint64_t *b_rep_off, const uint32_t *b_rep_len, const uint8_t *b_ent,
+                            const uint8_t *b_refused, uint8_t *replies, uint64_t rep_cap, uint64_t code_base,
+                            uint64_t *out_off, uint32_t *out_len, uint8_t *out_kind, uint64_t *result)
+{
+    LzfStitchArgs a{};
+    if (!stitch_args(a, op, status, slot, n, class_first, class_mode, class_base, b_rep_off, b_rep_len, b_ent,
+                         b_refused, replies, rep_cap, code_base, out_off, out_len, out_kind, result))
+        return LZF_GPU_EARG;
+    lzf_request_stitch_host(a);
+    return LZF_GPU_OK;
+}
+
 int lzf_gpu_store_count(const uint32_t *idx, uint32_t n, uint8_t *enc, uint32_t count,
                         const int64_t *item_time, const int32_t *item_ttl, int64_t now,
                         int64_t *last_access, uint64_t *result, void *stream)

@@ -181,6 +181,26 @@ struct LzfAppendArgs {
     uint64_t *w_state, *w_tile_n, *w_tile_b;
 };
 
+/* the bucket of a parsed batch by operator class (lzf_dispatch.hip); device
+ * pointers.  The first seven arrays are the parse's outputs, n entries; b_*
+ * their copies in bucket order */
+struct LzfBucketArgs {
+    const uint8_t *op, *status;
+    const uint64_t *key_off, *val_off;
+    const uint32_t *key_len, *val_len;
+    const int64_t *num;
+    uint32_t n;
+    uint32_t *perm, *slot, *class_first;
+    uint8_t *b_op, *b_status;
+    uint64_t *b_key_off, *b_val_off;
+    uint32_t *b_key_len, *b_val_len;
+    int64_t *b_num;
+    /* work area (lzf_bucket_layout): the classes x tiles table, class-major:
+     * per tile its requests of each class, after the scan the position in perm
+     * of the tile's first request of the class */
+    uint64_t *w_table;
+};
+
 /* the prefix select over the store's keys (lzf_mget.hip); device pointers */
 struct LzfSelectArgs {
     const uint8_t *keys;
@@ -454,6 +474,15 @@ hipError_t lzf_launch_request_parse(const LzfRequestArgs &a, hipStream_t s);
 hipError_t lzf_launch_store_append_keys(LzfAppendArgs &a, hipStream_t s);
 uint64_t lzf_append_work_bytes(uint32_t n);
 void lzf_append_carve(LzfAppendArgs &a, void *work);
+/* request dispatch (lzf_dispatch.hip): the stable partition of a parsed batch
+ * by operator class (the rule: lzf_request_class_of, lzf_request.h) with the
+ * seven arrays gathered into bucket order, and the reply table of a bucketed
+ * batch in request order */
+struct LzfStitchArgs;
+hipError_t lzf_launch_request_bucket(const LzfBucketArgs &a, hipStream_t s);
+hipError_t lzf_launch_request_stitch(const LzfStitchArgs &a, hipStream_t s);
+uint64_t lzf_bucket_work_bytes(uint32_t n);
+void lzf_bucket_carve(LzfBucketArgs &a, void *work);
 /* the operators over the store (lzf_mget.hip): the prefix select into an
  * index list, and MGET (`decode` over the gathered entries, in place in the
  * frame), COUNT and MTTL over an index list */

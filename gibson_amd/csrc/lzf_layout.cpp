@@ -1,5 +1,5 @@
 /*
- * lzf_layout.cpp -- the sizes and the carves of the device store's eleven work
+ * lzf_layout.cpp -- the sizes and the carves of the device store's twelve work
  * areas, each from its one layout (lzf_store_layout.h): the size is the layout
  * measured plus the slack for aligning the caller's pointer (64 bytes for the
  * frame, 16 for the others, as ever), the carve is the layout over that
@@ -73,6 +73,15 @@ uint64_t lzf_append_work_bytes(uint32_t n)
 }
 
 void lzf_append_carve(LzfAppendArgs &a, void *work) { carved(a, lzf_append_layout, work); }
+
+uint64_t lzf_bucket_work_bytes(uint32_t n)
+{
+    LzfBucketArgs a{};
+    a.n = n;
+    return measured(a, lzf_bucket_layout, 16u);
+}
+
+void lzf_bucket_carve(LzfBucketArgs &a, void *work) { carved(a, lzf_bucket_layout, work); }
 
 uint64_t lzf_select_work_bytes(uint32_t count)
 {

@@ -248,4 +248,165 @@ LZF_HD inline int lzf_request_reply_code_of(int status)
     }
 }
 
+/* The reply code of an operator's entry status, the single-key replies of
+ * gbQueryIncDecHandler and its kin (src/query.c:853-886): REPL_VAL for an
+ * entry the operator applied to, the error code of the others.  One rule for
+ * the reply kernels, the stitch and lzf_host_reply_code */
+LZF_HD inline int lzf_reply_code_of(int ent_status)
+{
+    switch (ent_status) {
+    case LZF_ENT_DONE:
+    case LZF_ENT_CONVERTED: return LZF_REPL_VAL;
+    case LZF_ENT_DEAD:
+    case LZF_ENT_EXPIRED: return LZF_REPL_ERR_NOT_FOUND;
+    case LZF_ENT_LOCKED: return LZF_REPL_ERR_LOCKED;
+    case LZF_ENT_NAN:
+    case LZF_ENT_UNCHANGED: return LZF_REPL_ERR_NAN;
+    default: return LZF_REPL_ERR;
+    }
+}
+
+/* ---- dispatch: the class rule, the bucket on the host, the stitch rule ------------
+ * (lzf_dispatch.hip has the kernels, lzf_api.cpp the calls, csrc/dispatch_check.cpp
+ * runs the host forms under the host sanitizers) */
+
+/* the class of a parsed request: 0 refused -- every status but OK and NAN, and
+ * an op the parse cannot yield; the operator itself, 1 .. 21, NAN travelling
+ * with it; LZF_RQ_NCLASS - 1 for END */
+LZF_HD inline uint32_t lzf_request_class_of(uint32_t op, uint32_t status)
+{
+    if (status != (uint32_t)LZF_REQ_OK && status != (uint32_t)LZF_REQ_NAN) return 0u;
+    if (op == (uint32_t)LZF_OP_END) return (uint32_t)LZF_RQ_NCLASS - 1u;
+    return op >= (uint32_t)LZF_OP_SET && op <= (uint32_t)LZF_OP_KEYS ? op : 0u;
+}
+
+/* lzf_host_request_bucket: a counting sort by class, stable; host pointers */
+inline void lzf_request_bucket_host(const uint8_t *op, const uint8_t *status, const uint64_t *key_off,
+                                    const uint32_t *key_len, const uint64_t *val_off, const uint32_t *val_len,
+                                    const int64_t *num, uint32_t n, uint32_t *perm, uint32_t *slot,
+                                    uint32_t *class_first, uint8_t *b_op, uint8_t *b_status, uint64_t *b_key_off,
+                                    uint32_t *b_key_len, uint64_t *b_val_off, uint32_t *b_val_len, int64_t *b_num)
+{
+    uint64_t at[LZF_RQ_NCLASS] = {0ull};
+    for (uint64_t k = 0; k < n; k++) at[lzf_request_class_of(op[k], status[k])]++;
+    uint64_t x = 0ull;
+    for (uint32_t c = 0; c < (uint32_t)LZF_RQ_NCLASS; c++) {
+        const uint64_t cnt = at[c];
+        class_first[c] = (uint32_t)x;
+        at[c] = x;
+        x += cnt;
+    }
+    class_first[LZF_RQ_NCLASS] = n;
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t j = at[lzf_request_class_of(op[k], status[k])]++;
+        perm[j] = (uint32_t)k;
+        slot[k] = (uint32_t)j;
+        b_op[j] = op[k];
+        b_status[j] = status[k];
+        b_key_off[j] = key_off[k];
+        b_key_len[j] = key_len[k];
+        b_val_off[j] = val_off[k];
+        b_val_len[j] = val_len[k];
+        b_num[j] = num[k];
+    }
+}
+
+/* the stitch of a bucketed batch's replies; device pointers for the kernel,
+ * host pointers for lzf_host_request_stitch.  class_mode and class_base travel
+ * by value */
+struct LzfStitchArgs {
+    const uint8_t *op, *status;
+    const uint32_t *slot, *class_first;
+    uint32_t n;
+    uint8_t class_mode[LZF_RQ_NCLASS];
+    uint64_t class_base[LZF_RQ_NCLASS];
+    const uint64_t *b_rep_off;
+    const uint32_t *b_rep_len;
+    const uint8_t *b_ent, *b_refused;
+    uint8_t *replies;
+    uint64_t rep_cap, code_base;
+    uint64_t *out_off;
+    uint32_t *out_len;
+    uint8_t *out_kind;
+    uint64_t *result;
+};
+
+/* what a request's reply is counted as: result[0 .. 3]; BAD is a code reply
+ * that also counts in result[4] */
+enum { LZF_ST_ARENA = 0, LZF_ST_CODE = 1, LZF_ST_CLOSE = 2, LZF_ST_HOST = 3, LZF_ST_BAD = 4, LZF_ST_NTALLY = 5 };
+
+#define LZF_STITCH_CODES 64u              /* the bytes of the code area */
+
+/* byte t of the code area: the frames of the codes 0 .. 6, [i16 code][u8
+ * PLAIN][u32 1][0x00] each (gbClientEnqueueCode, as lzf_reply.hip writes it),
+ * then 8 zero bytes */
+LZF_HD inline uint8_t lzf_stitch_code_byte(uint32_t t)
+{
+    const uint32_t code = t >> 3, b = t & 7u;
+    if (code > 6u) return 0u;
+    return b == 0u ? (uint8_t)code : b == 3u ? (uint8_t)1u : (uint8_t)0u;
+}
+
+/* request k's row of the reply table, the seven rules of include/lzf_gpu.h in
+ * their order; -> LZF_ST_* */
+LZF_HD inline uint32_t lzf_stitch_entry(const LzfStitchArgs &a, uint64_t k)
+{
+    const uint32_t op = a.op[k], st = a.status[k];
+    uint64_t off = 0ull;
+    uint32_t len = 0u, kind = LZF_OUT_REPLY, tally = LZF_ST_CODE;
+    int code = LZF_REPL_ERR;
+    if (st == (uint32_t)LZF_REQ_BADOP) {
+        kind = LZF_OUT_CLOSE;
+        tally = LZF_ST_CLOSE;
+    } else if (st == (uint32_t)LZF_REQ_OK || st == (uint32_t)LZF_REQ_NAN) {
+        const uint32_t c = lzf_request_class_of(op, st), mode = a.class_mode[c];
+        const uint64_t j = a.slot[k];
+        if (j < a.class_first[c] || j >= a.class_first[c + 1u] || j >= a.n) {
+            tally = LZF_ST_BAD;                               /* a table that contradicts itself: no b_* entry is read */
+        } else if (st == (uint32_t)LZF_REQ_NAN) {
+            const uint32_t ent = mode == (uint32_t)LZF_STITCH_CODE ? a.b_ent[j] : (uint32_t)LZF_ENT_DONE;
+            code = ent == (uint32_t)LZF_ENT_DEAD || ent == (uint32_t)LZF_ENT_EXPIRED ? LZF_REPL_ERR_NOT_FOUND
+                                                                                   : LZF_REPL_ERR_NAN;
+        } else if (mode == (uint32_t)LZF_STITCH_HOST) {
+            kind = LZF_OUT_HOST;
+            tally = LZF_ST_HOST;
+        } else if (op == (uint32_t)LZF_OP_SET && a.b_refused && a.b_refused[j]) {
+            code = LZF_REPL_ERR_LOCKED;
+        } else if (mode == (uint32_t)LZF_STITCH_ARENA) {
+            const uint64_t base = a.class_base[c], o = base + a.b_rep_off[j];
+            const uint32_t l = a.b_rep_len[j];
+            if (o >= base && o <= a.rep_cap && l <= a.rep_cap - o) {
+                off = o;
+                len = l;
+                tally = LZF_ST_ARENA;
+            } else {
+                tally = LZF_ST_BAD;
+            }
+        } else {
+            const int ent = a.b_ent[j];
+            code = ent == LZF_ENT_DONE || ent == LZF_ENT_CONVERTED ? LZF_REPL_OK : lzf_reply_code_of(ent);
+        }
+    }
+    if (tally == LZF_ST_CODE || tally == LZF_ST_BAD) {
+        off = a.code_base + 8ull * (uint32_t)code;
+        len = 8u;
+    }
+    a.out_off[k] = off;
+    a.out_len[k] = len;
+    a.out_kind[k] = (uint8_t)kind;
+    return tally;
+}
+
+/* lzf_host_request_stitch: the code area, then the same entry in a loop */
+inline void lzf_request_stitch_host(const LzfStitchArgs &a)
+{
+    for (uint32_t c = 0; c < LZF_ST_NTALLY; c++) a.result[c] = 0ull;
+    for (uint32_t t = 0; t < LZF_STITCH_CODES; t++) a.replies[a.code_base + t] = lzf_stitch_code_byte(t);
+    for (uint64_t k = 0; k < a.n; k++) {
+        const uint32_t t = lzf_stitch_entry(a, k);
+        a.result[t == LZF_ST_BAD ? LZF_ST_CODE : t]++;
+        if (t == LZF_ST_BAD) a.result[LZF_ST_BAD]++;
+    }
+}
+
 #endif

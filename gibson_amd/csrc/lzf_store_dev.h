@@ -1,7 +1,7 @@
 /*
  * lzf_store_dev.h -- the toolkit of the device store's kernels (lzf_frame.hip,
  * lzf_store.hip, lzf_mget.hip, lzf_kidx.hip, lzf_ops.hip, lzf_mset.hip,
- * lzf_meta.hip, lzf_reply.hip, lzf_renumber.hip, lzf_request.hip), over the byte helpers of
+ * lzf_meta.hip, lzf_reply.hip, lzf_renumber.hip, lzf_request.hip, lzf_dispatch.hip), over the byte helpers of
  * lzf_dev.h, the geometry of lzf_store_layout.h and the request grammar of
  * lzf_request.h, where the number parse lives.  One copy of each: the pad and the "no
  * entry" class; the ballot count, the 64-bit wave sum and the wave leader's
@@ -234,22 +234,7 @@ __device__ inline uint32_t sd_entry_class(uint32_t i, const LzfItems &it, bool e
 /* the number parse, gbQueryParseLong: lzf_parse_long of lzf_request.h, beside
  * the request grammar that needs it on the host too */
 
-/* The reply code of an operator's entry status, the single-key replies of
- * gbQueryIncDecHandler and its kin (src/query.c:853-886): REPL_VAL for an
- * entry the operator applied to, the error code of the others.  One rule for
- * the reply kernels and lzf_host_reply_code */
-__host__ __device__ inline int lzf_reply_code_of(int ent_status)
-{
-    switch (ent_status) {
-    case LZF_ENT_DONE:
-    case LZF_ENT_CONVERTED: return LZF_REPL_VAL;
-    case LZF_ENT_DEAD:
-    case LZF_ENT_EXPIRED: return LZF_REPL_ERR_NOT_FOUND;
-    case LZF_ENT_LOCKED: return LZF_REPL_ERR_LOCKED;
-    case LZF_ENT_NAN:
-    case LZF_ENT_UNCHANGED: return LZF_REPL_ERR_NAN;
-    default: return LZF_REPL_ERR;
-    }
-}
+/* the reply code of an operator's entry status: lzf_reply_code_of of
+ * lzf_request.h, beside the stitch rule that needs it on the host too */
 
 #endif

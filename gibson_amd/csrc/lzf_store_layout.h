@@ -13,6 +13,7 @@
 
 #include "lzf_internal.h"
 #include "gb_policy.h"
+#include "../../include/lzf_gpu.h"
 
 /* The one geometry of the store's kernels (lzf_store_dev.h has the device
  * side): workgroups of 256 threads, 4 waves; a scan tile is 4 neighbouring
@@ -154,6 +155,14 @@ static inline void lzf_append_layout(LzfAppendArgs &a, LzfCarver &c)
     a.w_state = c.take<uint64_t>(SD_STATE_WORDS);
     a.w_tile_n = c.take<uint64_t>(nt);
     a.w_tile_b = c.take<uint64_t>(nt);
+}
+
+/* request_bucket (lzf_dispatch.hip): one count per class and scan tile, u64 as
+ * dv_carry_scan scans them in place */
+static inline void lzf_bucket_layout(LzfBucketArgs &a, LzfCarver &c)
+{
+    c.align(8);
+    a.w_table = c.take<uint64_t>((uint64_t)LZF_RQ_NCLASS * sd_tiles(a.n));
 }
 
 /* select (lzf_mget.hip) */

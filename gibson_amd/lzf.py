@@ -93,6 +93,12 @@ EXPORTS = (
     "lzf_host_request_reply_code",
     "lzf_gpu_store_append_keys_work_size",
     "lzf_gpu_store_append_keys",
+    "lzf_host_request_class",
+    "lzf_gpu_request_bucket_work_size",
+    "lzf_gpu_request_bucket",
+    "lzf_host_request_bucket",
+    "lzf_gpu_request_stitch",
+    "lzf_host_request_stitch",
 )
 
 # size classes of the mixed calls (include/lzf_gpu.h)
@@ -131,6 +137,10 @@ REPL_ERR, REPL_ERR_NOT_FOUND, REPL_ERR_NAN, REPL_ERR_LOCKED, REPL_OK, REPL_VAL =
 OP_END = 0xFF
 REQ_OK, REQ_ERR, REQ_NAN, REQ_BADOP, REQ_SHORT, REQ_ERANGE, REQ_OTHER = 0, 1, 2, 3, 4, 5, 6
 REQ_NSTATUS = 7
+# request dispatch: the classes of request_bucket, class_mode and out_kind of request_stitch
+RQ_NCLASS = 23
+STITCH_HOST, STITCH_ARENA, STITCH_CODE = 0, 1, 2
+OUT_REPLY, OUT_CLOSE, OUT_HOST = 0, 1, 2
 
 
 class LzfLibraryMissing(ImportError):
@@ -250,6 +260,8 @@ def _load(path):
         _bind_store_renumber(L)
     if hasattr(L, "lzf_gpu_request_parse"):
         _bind_request(L)
+    if hasattr(L, "lzf_gpu_request_bucket"):
+        _bind_dispatch(L)
     del i32
     _LOADED[path] = L
     return L
@@ -349,6 +361,25 @@ def _bind_request(L):
     L.lzf_gpu_store_append_keys.restype = ctypes.c_int
     L.lzf_gpu_store_append_keys.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp,
                                             u32, u32, i64, i32, vp, vp, vp, vp, vp]
+
+
+def _bind_dispatch(L):
+    """Request dispatch: the bucket of a parsed batch by operator class and the
+    stitch of its replies; absent from an older build given by LZF_HIP_LIB (the
+    helpers below then raise AttributeError)."""
+    u32, u64, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
+    L.lzf_host_request_class.restype = ctypes.c_int
+    L.lzf_host_request_class.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.lzf_gpu_request_bucket_work_size.restype = u64
+    L.lzf_gpu_request_bucket_work_size.argtypes = [u32]
+    L.lzf_gpu_request_bucket.restype = ctypes.c_int
+    L.lzf_gpu_request_bucket.argtypes = [vp] * 7 + [u32] + [vp] * 10 + [vp, vp]
+    L.lzf_host_request_bucket.restype = ctypes.c_int
+    L.lzf_host_request_bucket.argtypes = [vp] * 7 + [u32] + [vp] * 10
+    L.lzf_gpu_request_stitch.restype = ctypes.c_int
+    L.lzf_gpu_request_stitch.argtypes = [vp, vp, vp, u32] + [vp] * 8 + [u64, u64, vp, vp, vp, vp, vp]
+    L.lzf_host_request_stitch.restype = ctypes.c_int
+    L.lzf_host_request_stitch.argtypes = [vp, vp, vp, u32] + [vp] * 8 + [u64, u64, vp, vp, vp, vp]
 
 
 def _bind_store_index(L):
@@ -1212,6 +1243,135 @@ def store_append_keys(req, parsed, keys, keys_used, key_off, key_len, first, now
                                          _ptr(work), _stream_handle(stream))
     _check(rc, "lzf_gpu_store_append_keys")
     return work
+
+
+# ---- request dispatch: bucket a mixed batch by operator, stitch the replies ----------
+
+def request_class(op, status):
+    """lzf_host_request_class: 0 for a refused request (every status but
+    REQ_OK and REQ_NAN), the operator 1 .. 21 itself, RQ_NCLASS - 1 for OP_END.
+    No device call."""
+    return int(lib().lzf_host_request_class(int(op), int(status)))
+
+
+class BucketedRequests:
+    """What request_bucket makes of a ParsedRequests of n entries: perm and
+    slot (int32 read as u32, n each; perm[slot[k]] == k), class_first
+    (RQ_NCLASS + 1, int32) and ``b``, a ParsedRequests in bucket order.  Class
+    c is the slice ``class_slice(c, first)`` of perm and of every array of
+    ``b``, ``first`` being class_first copied to the host.  Tensors on one
+    device, or numpy arrays from host_request_bucket."""
+
+    def __init__(self, perm, slot, class_first, b):
+        self.perm, self.slot, self.class_first, self.b = perm, slot, class_first, b
+
+    @classmethod
+    def empty(cls, n, device):
+        import torch
+        i32 = lambda k: torch.empty(k, dtype=torch.int32, device=device)
+        return cls(i32(n), i32(n), i32(RQ_NCLASS + 1), ParsedRequests.empty(n, device))
+
+    @staticmethod
+    def class_slice(c, first):
+        return slice(int(first[c]), int(first[c + 1]))
+
+
+def request_bucket_work(n, device):
+    """A scratch tensor for one request_bucket call over ``n`` requests."""
+    import torch
+    return torch.empty(int(lib().lzf_gpu_request_bucket_work_size(int(n))), dtype=torch.uint8, device=device)
+
+
+def request_bucket(parsed, out, work=None, stream=None):
+    """The stable partition of a parsed batch by operator class
+    (request_class): ``out`` (a BucketedRequests) receives perm, slot,
+    class_first and the seven arrays in bucket order, whose class slices feed
+    key_index_lookup, store_append_keys and set_store as they are.  No host
+    wait; the caller copies class_first (96 bytes) to size its per-class
+    calls.  Returns ``work`` (request_bucket_work), which must outlive the
+    stream's work."""
+    n = parsed.status.numel()
+    if work is None:
+        work = request_bucket_work(n, parsed.status.device)
+    b = out.b
+    rc = lib().lzf_gpu_request_bucket(_ptr(parsed.op), _ptr(parsed.status), _ptr(parsed.key_off), _ptr(parsed.key_len),
+                                      _ptr(parsed.val_off), _ptr(parsed.val_len), _ptr(parsed.num), n, _ptr(out.perm),
+                                      _ptr(out.slot), _ptr(out.class_first), _ptr(b.op), _ptr(b.status),
+                                      _ptr(b.key_off), _ptr(b.key_len), _ptr(b.val_off), _ptr(b.val_len), _ptr(b.num),
+                                      _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_request_bucket")
+    return work
+
+
+_PARSED_NP = (("op", "uint8"), ("status", "uint8"), ("key_off", "uint64"), ("key_len", "uint32"),
+              ("val_off", "uint64"), ("val_len", "uint32"), ("num", "int64"))
+
+
+def host_request_bucket(parsed):
+    """request_bucket on the host over a ParsedRequests of numpy arrays (a
+    counting sort): a BucketedRequests of numpy arrays, perm / slot /
+    class_first uint32.  No GPU."""
+    import numpy as np
+    src = [np.ascontiguousarray(getattr(parsed, f), dtype=dt) for f, dt in _PARSED_NP]
+    n = len(src[0])
+    out = BucketedRequests(np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(RQ_NCLASS + 1, np.uint32),
+                           ParsedRequests(*(np.zeros(n, dtype=dt) for _, dt in _PARSED_NP)))
+    rc = lib().lzf_host_request_bucket(*(_np_ptr(a) for a in src), n, _np_ptr(out.perm), _np_ptr(out.slot),
+                                       _np_ptr(out.class_first), *(_np_ptr(getattr(out.b, f)) for f, _ in _PARSED_NP))
+    _check(rc, "lzf_host_request_bucket")
+    return out
+
+
+def _stitch_tables(class_mode, class_base):
+    if len(class_mode) != RQ_NCLASS or len(class_base) != RQ_NCLASS:
+        raise ValueError("class_mode and class_base have RQ_NCLASS entries")
+    return ((ctypes.c_uint8 * RQ_NCLASS)(*(int(m) for m in class_mode)),
+            (ctypes.c_uint64 * RQ_NCLASS)(*(int(b) for b in class_base)))
+
+
+def request_stitch(op, status, slot, class_first, class_mode, class_base, replies, code_base, out_off, out_len,
+                   out_kind, result, b_rep_off=None, b_rep_len=None, b_ent=None, b_refused=None, stream=None):
+    """The reply table of a bucketed batch in request order, the overrides made
+    on the device: request k gets out_off[k] (int64, absolute into ``replies``),
+    out_len[k] (int32) and out_kind[k] (uint8: OUT_REPLY, OUT_CLOSE, OUT_HOST)
+    by the seven rules of include/lzf_gpu.h.  class_mode (STITCH_*) and
+    class_base are host sequences of RQ_NCLASS entries; b_rep_off / b_rep_len
+    (what store_replies wrote, at each ARENA class's slice), b_ent (ENT_*, at
+    each CODE class's slice) and b_refused (store_set_guard's, at the SET
+    slice) are in bucket order.  The 64 bytes of ``replies`` at code_base
+    receive the code frames.  result (5 elements, int64) = arena replies, code
+    replies, closes, host, bad slices.  No reply byte is copied.  No host wait."""
+    mode, base = _stitch_tables(class_mode, class_base)
+    rc = lib().lzf_gpu_request_stitch(_ptr(op), _ptr(status), _ptr(slot), int(status.numel()), _ptr(class_first),
+                                      mode, base, _opt_ptr(b_rep_off), _opt_ptr(b_rep_len), _opt_ptr(b_ent),
+                                      _opt_ptr(b_refused), _ptr(replies), int(replies.numel()), int(code_base),
+                                      _ptr(out_off), _ptr(out_len), _ptr(out_kind), _ptr(result),
+                                      _stream_handle(stream))
+    _check(rc, "lzf_gpu_request_stitch")
+
+
+def host_request_stitch(op, status, slot, class_first, class_mode, class_base, replies, code_base, b_rep_off=None,
+                        b_rep_len=None, b_ent=None, b_refused=None):
+    """request_stitch on the host over numpy arrays (``replies`` a writable
+    uint8 array, which receives the code frames): (out_off uint64, out_len
+    uint32, out_kind uint8, result uint64).  No GPU."""
+    import numpy as np
+    mode, base = _stitch_tables(class_mode, class_base)
+    arr = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+    op, status, slot = arr(op, np.uint8), arr(status, np.uint8), arr(slot, np.uint32)
+    class_first = arr(class_first, np.uint32)
+    b_rep_off, b_rep_len = arr(b_rep_off, np.uint64), arr(b_rep_len, np.uint32)
+    b_ent, b_refused = arr(b_ent, np.uint8), arr(b_refused, np.uint8)
+    n = len(status)
+    out_off, out_len, out_kind = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+    result = np.zeros(5, np.uint64)
+    opt = lambda a: ctypes.c_void_p(0) if a is None else _np_ptr(a)
+    rc = lib().lzf_host_request_stitch(_np_ptr(op), _np_ptr(status), _np_ptr(slot), n, _np_ptr(class_first), mode, base,
+                                       opt(b_rep_off), opt(b_rep_len), opt(b_ent), opt(b_refused), _np_ptr(replies),
+                                       len(replies), int(code_base), _np_ptr(out_off), _np_ptr(out_len),
+                                       _np_ptr(out_kind), _np_ptr(result))
+    _check(rc, "lzf_host_request_stitch")
+    return out_off, out_len, out_kind, result
 
 
 # ---- MSET by prefix, the memory sweep, META and the KEYS frame --------------------

@@ -1320,6 +1320,159 @@ int lzf_gpu_store_append_keys(const uint8_t *req, uint64_t req_bytes,
                               uint32_t *set_len /* n */, uint32_t *void_idx /* n */,
                               uint64_t *result /* 4 u64 */, void *work, void *stream);
 
+/*
+ * Request dispatch: a parsed batch of mixed operators bucketed by operator on
+ * the device, and the per-operator replies stitched back into request order,
+ * so that one event-loop tick goes sockets -> one arena -> parse (expect_op =
+ * 0) -> bucket -> per-operator calls -> stitch -> one copy, with the host
+ * reading no request and overriding no reply.
+ *
+ * The class rule, lzf_host_request_class(op, status), LZF_RQ_NCLASS = 23
+ * classes:
+ *   0        refused: every status but LZF_REQ_OK and LZF_REQ_NAN (and an op
+ *            the parse cannot yield: 0, 22 .. 254);
+ *   1 .. 21  the operator itself, for status OK or NAN -- NAN keeps its spans
+ *            and travels with its operator, because the TTL and LOCK handlers
+ *            look the key up before they test the number;
+ *   22       LZF_OP_END.
+ *
+ * lzf_gpu_request_bucket takes the seven outputs of a parse of n requests and
+ * writes, all in device memory:
+ *   perm[n]         request indices, class-major; inside a class the request
+ *                   order is kept (a stable partition);
+ *   slot[n]         the inverse, perm[slot[k]] == k;
+ *   class_first[LZF_RQ_NCLASS + 1]
+ *                   class c is perm[class_first[c] .. class_first[c + 1]),
+ *                   class_first[LZF_RQ_NCLASS] == n;
+ *   b_op .. b_num   the seven arrays in bucket order, b_x[j] = x[perm[j]].
+ * Class c's slice is pointer + class_first[c] with class_first[c + 1] -
+ * class_first[c] entries and feeds the calls above as it is, the offsets still
+ * absolute into the request arena: b_key_off / b_key_len are
+ * lzf_gpu_key_index_lookup's q_off / q_len; the SET slice has op == SET
+ * throughout and status OK but for its NAN requests, which
+ * lzf_gpu_store_append_keys refuses one by one, and b_val_off is
+ * lzf_gpu_set_store's in_off.
+ *
+ * Asynchronous on `stream`, with no host wait inside the call.  The caller
+ * copies the 96 bytes of class_first to size its per-class launches: one small
+ * wait per batch, as lzf_gpu_*_mixed takes for its 48 bytes.  n up to 2^32 - 1,
+ * 64-bit byte arithmetic.  LZF_GPU_EARG, before any HIP call: a NULL pointer,
+ * n == 0.  `work`: lzf_gpu_request_bucket_work_size(n) bytes of device scratch
+ * that must stay valid until the stream's work is done.
+ * lzf_host_request_bucket is the same partition as a counting sort over host
+ * arrays, with no HIP call.
+ *
+ * lzf_gpu_request_stitch builds the reply table in request order and makes
+ * the overrides on the device.  It copies no reply byte: a client's reply
+ * stays a slice of the one device-to-host copy of replies[0 .. rep_cap).
+ * Inputs: op, status, slot (request order, n entries) and class_first (device);
+ * class_mode and class_base, two HOST arrays of LZF_RQ_NCLASS entries that
+ * travel in the kernel's arguments -- class_mode[c] is LZF_STITCH_HOST (the
+ * host builds the class's replies: PING, STATS, END, the ordered prefix walk),
+ * LZF_STITCH_ARENA (lzf_gpu_store_replies wrote them) or LZF_STITCH_CODE (the
+ * class left an entry status), class_base[c] is where class c's reply arena
+ * starts inside `replies`; and in bucket order, n entries each, b_rep_off /
+ * b_rep_len (what lzf_gpu_store_replies wrote for each ARENA class, at the
+ * class's slice), b_ent (LZF_ENT_*: what lzf_gpu_store_mdel / _mlock /
+ * _munlock left for each CODE class; may be NULL when no class is CODE) and
+ * b_refused (lzf_gpu_store_set_guard's output at the SET slice; may be NULL).
+ * code_base: 64 bytes of `replies` where the call writes the code frames of
+ * the codes 0 .. 6, 8 bytes each, [i16 code][u8 PLAIN][u32 1][0x00]
+ * (gbClientEnqueueCode's form); the frame of code c is at code_base + 8 c and
+ * the last 8 bytes are zero.
+ *
+ * Request k, with j = slot[k] and c its class; the first rule that matches:
+ *   1. status BADOP                    LZF_OUT_CLOSE, offset and length 0
+ *   2. a status other than OK / NAN    the REPL_ERR frame
+ *   3. NAN                             REPL_ERR_NOT_FOUND if c is CODE and
+ *                                      b_ent[j] is DEAD or EXPIRED, otherwise
+ *                                      REPL_ERR_NAN
+ *   4. class_mode[c] == HOST           LZF_OUT_HOST, offset and length 0
+ *   5. op SET, b_refused given and b_refused[j] != 0
+ *                                      REPL_ERR_LOCKED
+ *   6. ARENA                           out_off = class_base[c] + b_rep_off[j],
+ *                                      out_len = b_rep_len[j]; a slice that
+ *                                      leaves [0, rep_cap) or wraps (64-bit)
+ *                                      becomes the REPL_ERR frame and counts
+ *                                      in result[4]
+ *   7. CODE                            DONE / CONVERTED -> REPL_OK, anything
+ *                                      else lzf_host_reply_code(b_ent[j])
+ * A table that contradicts itself -- status OK or NAN and slot[k] outside its
+ * class's range of class_first, or >= n -- is treated as a bad slice after rule
+ * 2 (REPL_ERR, counted in result[4]); no b_* entry is read for it.
+ *
+ * Outputs, request order: out_off (u64, absolute into replies), out_len (u32),
+ * out_kind (u8, LZF_OUT_*).  result (5 device u64): [0] arena replies, [1]
+ * code replies, [2] closes, [3] host, [4] bad slices (they are among [1]);
+ * [0] + [1] + [2] + [3] == n.  Nothing is written outside the three output
+ * arrays, result and the 64 code bytes.  LZF_GPU_EARG, before any HIP call: a
+ * NULL required pointer, n == 0, a mode above 2, an ARENA class with b_rep_off
+ * or b_rep_len NULL, a CODE class with b_ent NULL, code_base + 64 > rep_cap
+ * (64-bit, wrap-safe).  Asynchronous on `stream`, with no host wait.
+ * lzf_host_request_stitch is the same function in a host loop over host
+ * arrays, with no HIP call.
+ *
+ * A mixed batch on one stream: lzf_gpu_request_parse(expect_op = 0) ->
+ * lzf_gpu_request_bucket -> copy class_first -> per class, in an order the
+ * caller chooses, the calls above over the class's slices (SET: the eight
+ * steps of lzf_gpu_store_append_keys' contract; GET: lookup ->
+ * lzf_gpu_store_replies; DEL / LOCK / UNLOCK: lookup -> lzf_gpu_store_mdel /
+ * _mlock / _munlock with entry_status), each ARENA class into its own range
+ * of `replies` -> lzf_gpu_request_stitch -> one copy of replies and the table.
+ *
+ * The batch's serial order.  A bucketed batch executes class by class in the
+ * order the caller launches the classes, and inside a class in request order:
+ * that is one serial order of the batch.  It is a legal outcome of the
+ * reference server exactly when no client has two requests in the batch --
+ * requests of different clients in one tick have no order a client can
+ * observe -- so a client's next request waits for the next batch.  Limits:
+ * the index-list operators leave duplicates unspecified, so two DELs or INCs
+ * of one key in one batch are the host's to split; the prefix operators'
+ * reply order (MGET with a limit, KEYS) still needs the host's trie.
+ */
+#define LZF_RQ_NCLASS      23
+
+#define LZF_STITCH_HOST    0
+#define LZF_STITCH_ARENA   1
+#define LZF_STITCH_CODE    2
+
+#define LZF_OUT_REPLY      0   /* out_len bytes at replies + out_off */
+#define LZF_OUT_CLOSE      1   /* close the connection (gbProcessQuery returns GB_ERR) */
+#define LZF_OUT_HOST       2   /* the host builds this reply */
+
+/* host, no HIP call: the class of (op, status), 0 .. LZF_RQ_NCLASS - 1 */
+int lzf_host_request_class(int op, int status);
+uint64_t lzf_gpu_request_bucket_work_size(uint32_t n);
+int lzf_gpu_request_bucket(const uint8_t *op, const uint8_t *status,
+                           const uint64_t *key_off, const uint32_t *key_len,
+                           const uint64_t *val_off, const uint32_t *val_len, const int64_t *num, uint32_t n,
+                           uint32_t *perm /* n */, uint32_t *slot /* n */,
+                           uint32_t *class_first /* LZF_RQ_NCLASS + 1 */,
+                           uint8_t *b_op, uint8_t *b_status, uint64_t *b_key_off, uint32_t *b_key_len,
+                           uint64_t *b_val_off, uint32_t *b_val_len, int64_t *b_num,
+                           void *work, void *stream);
+int lzf_host_request_bucket(const uint8_t *op, const uint8_t *status,
+                            const uint64_t *key_off, const uint32_t *key_len,
+                            const uint64_t *val_off, const uint32_t *val_len, const int64_t *num, uint32_t n,
+                            uint32_t *perm, uint32_t *slot, uint32_t *class_first,
+                            uint8_t *b_op, uint8_t *b_status, uint64_t *b_key_off, uint32_t *b_key_len,
+                            uint64_t *b_val_off, uint32_t *b_val_len, int64_t *b_num);
+int lzf_gpu_request_stitch(const uint8_t *op, const uint8_t *status, const uint32_t *slot, uint32_t n,
+                           const uint32_t *class_first /* device, LZF_RQ_NCLASS + 1 */,
+                           const uint8_t *class_mode /* host, LZF_RQ_NCLASS */,
+                           const uint64_t *class_base /* host, LZF_RQ_NCLASS */,
+                           const uint64_t *b_rep_off, const uint32_t *b_rep_len,
+                           const uint8_t *b_ent /* may be NULL */, const uint8_t *b_refused /* may be NULL */,
+                           uint8_t *replies, uint64_t rep_cap, uint64_t code_base,
+                           uint64_t *out_off /* n */, uint32_t *out_len /* n */, uint8_t *out_kind /* n */,
+                           uint64_t *result /* 5 u64 */, void *stream);
+int lzf_host_request_stitch(const uint8_t *op, const uint8_t *status, const uint32_t *slot, uint32_t n,
+                            const uint32_t *class_first, const uint8_t *class_mode, const uint64_t *class_base,
+                            const uint64_t *b_rep_off, const uint32_t *b_rep_len,
+                            const uint8_t *b_ent, const uint8_t *b_refused,
+                            uint8_t *replies, uint64_t rep_cap, uint64_t code_base,
+                            uint64_t *out_off, uint32_t *out_len, uint8_t *out_kind, uint64_t *result);
+
 /* Free the library's device scratch (all devices), the calling thread's and
  * the device workers' staging buffers; later calls allocate them again.
  * Each thread's staging buffers are also freed when the thread exits. */
