@@ -159,6 +159,38 @@ int main()
             fill("select.w_tile", a.w_tile, nt);
             settle("select", n);
         });
+        /* select_ordered: the candidate cap below, at and above n; the node cap small and large */
+        for (const uint32_t cn : {1u, n, n + 1000u})
+            for (const uint64_t nodes : {(uint64_t)1u, (uint64_t)3u * n, (uint64_t)4096u})
+                at_every_misalignment(lzf_order_work_bytes(n, cn, nodes, 7u), [&](void *work) {
+                    LzfOrderArgs a{};
+                    a.count = n;
+                    a.cand_cap = cn;
+                    a.node_cap = nodes;
+                    lzf_order_carve(a, work);
+                    const uint64_t ct = sd_tiles(cn);
+                    if (a.slots < 2u * nodes || (a.slots & (a.slots - 1u))) {
+                        fprintf(stderr, "carve_check: order.slots %llu for %llu node words\n",
+                                (unsigned long long)a.slots, (unsigned long long)nodes);
+                        g_bad = 1;
+                    }
+                    fill("order.w_state", a.w_state, SD_STATE_WORDS);
+                    fill("order.w_mask", a.w_mask, nt * SD_WORDS);
+                    fill("order.w_tile_n", a.w_tile_n, nt);
+                    fill("order.w_tile_b", a.w_tile_b, nt);
+                    fill("order.w_tile_m", a.w_tile_m, nt);
+                    fill("order.w_table", a.w_table, a.slots);
+                    fill("order.w_ctile_n", a.w_ctile_n, ct);
+                    fill("order.w_ctile_b", a.w_ctile_b, ct);
+                    fill("order.w_row_off", a.w_row_off, cn);
+                    fill("order.w_rows", a.w_rows, nodes);
+                    fill("order.w_cand", a.w_cand, cn);
+                    fill("order.w_live", a.w_live, cn);
+                    fill("order.w_row_len", a.w_row_len, cn);
+                    fill("order.w_sort0", a.w_sort[0], cn);
+                    fill("order.w_sort1", a.w_sort[1], cn);
+                    settle("order", n);
+                });
         at_every_misalignment(lzf_mget_work_bytes(n), [&](void *work) {
             LzfMgetArgs a{};
             a.n = n;

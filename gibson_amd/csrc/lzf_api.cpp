@@ -25,6 +25,7 @@
 
 #include "lzf_internal.h"
 #include "lzf_request.h"
+#include "lzf_order.h"
 #include "../../include/lzf.h"
 #include "../../include/lzf_gpu.h"
 
@@ -957,6 +958,42 @@ int lzf_gpu_store_select_prefix(const uint8_t *keys, const uint64_t *key_off, co
     a.sel = sel; a.cap = cap; a.result = result;
     lzf_select_carve(a, work);
     return rc_of(lzf_launch_store_select(a, (hipStream_t)stream));
+}
+
+uint64_t lzf_gpu_store_select_ordered_work_size(uint32_t count, uint32_t cand_cap, uint64_t node_cap, uint32_t cap)
+{
+    return lzf_order_work_bytes(count, cand_cap, node_cap, cap);
+}
+
+int lzf_gpu_store_select_ordered(const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                                 const uint8_t *enc, uint32_t count,
+                                 const uint8_t *prefix, uint32_t prefix_len, int64_t limit,
+                                 uint32_t cand_cap, uint64_t node_cap,
+                                 uint32_t *sel, uint32_t cap, uint64_t *result, void *work, void *stream)
+{
+    if (!keys || !key_off || !key_len || !enc || !prefix || !sel || !result || !work) return LZF_GPU_EARG;
+    if (!count || !prefix_len || !cap || !cand_cap || !node_cap) return LZF_GPU_EARG;
+    if (lzf_order_work_bytes(count, cand_cap, node_cap, cap) == ~0ull) return LZF_GPU_EARG;
+    if (const int rc = current_device_ok()) return rc;
+    LzfOrderArgs a{};
+    a.keys = keys; a.key_off = key_off; a.key_len = key_len; a.enc = enc; a.count = count;
+    a.prefix = prefix; a.prefix_len = prefix_len; a.limit = limit;
+    a.cand_cap = cand_cap; a.node_cap = node_cap;
+    a.sel = sel; a.cap = cap; a.result = result;
+    lzf_order_carve(a, work);
+    return rc_of(lzf_launch_store_select_ordered(a, (hipStream_t)stream));
+}
+
+int lzf_host_store_select_ordered(const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                                  const uint8_t *enc, uint32_t count,
+                                  const uint8_t *prefix, uint32_t prefix_len, int64_t limit,
+                                  uint32_t cand_cap, uint64_t node_cap,
+                                  uint32_t *sel, uint32_t cap, uint64_t *result)
+{
+    if (!keys || !key_off || !key_len || !enc || !prefix || !sel || !result) return LZF_GPU_EARG;
+    if (!count || !prefix_len || !cap || !cand_cap || !node_cap) return LZF_GPU_EARG;
+    return lzf_order_host(keys, key_off, key_len, enc, count, prefix, prefix_len, limit, cand_cap, node_cap, sel,
+                          cap, result);
 }
 
 uint64_t lzf_gpu_store_mget_work_size(uint32_t n)

@@ -218,6 +218,36 @@ struct LzfSelectArgs {
     uint64_t *w_mask, *w_tile;
 };
 
+/* the ordered prefix select (lzf_order.hip); device pointers.  Candidates are
+ * the items whose key starts with the prefix, dead ones included; matches are
+ * the live candidates */
+struct LzfOrderArgs {
+    const uint8_t *keys;
+    const uint64_t *key_off;
+    const uint32_t *key_len;
+    const uint8_t *enc;
+    uint32_t count;
+    const uint8_t *prefix;
+    uint32_t prefix_len;
+    int64_t limit;
+    uint32_t cand_cap;
+    uint64_t node_cap;
+    uint32_t *sel;
+    uint32_t cap;
+    uint64_t *result;
+    /* work area (lzf_order_layout).  w_state: the OD_* words of lzf_order.hip.
+     * w_mask / w_tile_n / w_tile_b / w_tile_m: per 64 items the candidates'
+     * ballot, per item tile [live:32 | candidates:32], the candidates' node
+     * words and their longest key.  w_table: the node table, `slots` words.
+     * w_cand: the candidate list.  w_ctile_n / w_ctile_b: per tile of the
+     * candidate list its matches and their row words.  w_live, w_row_off,
+     * w_row_len: per match its item, and its row in w_rows.  w_sort: the two
+     * index buffers of the sort */
+    uint64_t slots;
+    uint64_t *w_state, *w_mask, *w_tile_n, *w_tile_b, *w_tile_m, *w_table, *w_ctile_n, *w_ctile_b, *w_row_off;
+    uint32_t *w_cand, *w_live, *w_row_len, *w_rows, *w_sort[2];
+};
+
 /* MGET over an index list (lzf_mget.hip); device pointers */
 struct LzfMgetArgs {
     const uint32_t *idx;
@@ -489,6 +519,11 @@ void lzf_bucket_carve(LzfBucketArgs &a, void *work);
 hipError_t lzf_launch_store_select(LzfSelectArgs &a, hipStream_t s);
 uint64_t lzf_select_work_bytes(uint32_t count);
 void lzf_select_carve(LzfSelectArgs &a, void *work);
+/* the ordered prefix select (lzf_order.hip): the live matches in the
+ * reference's trie order */
+hipError_t lzf_launch_store_select_ordered(LzfOrderArgs &a, hipStream_t s);
+uint64_t lzf_order_work_bytes(uint32_t count, uint32_t cand_cap, uint64_t node_cap, uint32_t cap);
+void lzf_order_carve(LzfOrderArgs &a, void *work);
 hipError_t lzf_launch_store_mget(LzfMgetArgs &a, hipStream_t s, hipError_t (*decode)(const LzfBatch &, hipStream_t));
 uint64_t lzf_mget_work_bytes(uint32_t n);
 void lzf_mget_carve(LzfMgetArgs &a, void *work);

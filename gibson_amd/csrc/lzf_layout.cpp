@@ -1,5 +1,5 @@
 /*
- * lzf_layout.cpp -- the sizes and the carves of the device store's twelve work
+ * lzf_layout.cpp -- the sizes and the carves of the device store's thirteen work
  * areas, each from its one layout (lzf_store_layout.h): the size is the layout
  * measured plus the slack for aligning the caller's pointer (64 bytes for the
  * frame, 16 for the others, as ever), the carve is the layout over that
@@ -91,6 +91,19 @@ uint64_t lzf_select_work_bytes(uint32_t count)
 }
 
 void lzf_select_carve(LzfSelectArgs &a, void *work) { carved(a, lzf_select_layout, work); }
+
+/* cap sizes nothing: sel is the caller's, and the sort works on cand_cap */
+uint64_t lzf_order_work_bytes(uint32_t count, uint32_t cand_cap, uint64_t node_cap, uint32_t cap)
+{
+    (void)cap;
+    LzfOrderArgs a{};
+    a.count = count;
+    a.cand_cap = cand_cap;
+    a.node_cap = node_cap;
+    return measured(a, lzf_order_layout, 16u);
+}
+
+void lzf_order_carve(LzfOrderArgs &a, void *work) { carved(a, lzf_order_layout, work); }
 
 uint64_t lzf_mget_work_bytes(uint32_t n)
 {

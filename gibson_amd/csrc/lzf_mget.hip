@@ -58,21 +58,7 @@ enum { MG_PAYLOAD = 0, MG_STATUS = 1, MG_FOUND = 2, MG_BAD = 3 };
 
 /* ---- select ----------------------------------------------------------------- */
 
-/* whether the plen bytes at key equal the prefix: whole dwords, the last one
- * overlapping the one before it when plen is no multiple of 4, so only a
- * prefix of 1-3 bytes is compared byte by byte.  Most keys leave at the first
- * dword */
-__device__ inline bool mg_prefix_match(const uint8_t *key, const uint8_t *__restrict__ prefix, uint32_t plen)
-{
-    if (plen < 4u) {
-        bool same = true;
-        for (uint32_t j = 0; j < plen; j++) same &= key[j] == prefix[j];
-        return same;
-    }
-    for (uint32_t j = 0; j + 4u <= plen; j += 4u)
-        if (dv_ld4(key + j) != dv_ld4(prefix + j)) return false;
-    return !(plen & 3u) || dv_ld4(key + plen - 4u) == dv_ld4(prefix + plen - 4u);
-}
+/* mg_prefix_match, the prefix test of both selects: lzf_store_dev.h */
 
 /* item i of a tile sits in round k = (i % SD_TILE) / SD_BLOCK at thread
  * i % SD_BLOCK, so a wave reads 64 neighbouring descriptors and its ballot

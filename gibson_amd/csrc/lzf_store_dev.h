@@ -1,7 +1,8 @@
 /*
  * lzf_store_dev.h -- the toolkit of the device store's kernels (lzf_frame.hip,
  * lzf_store.hip, lzf_mget.hip, lzf_kidx.hip, lzf_ops.hip, lzf_mset.hip,
- * lzf_meta.hip, lzf_reply.hip, lzf_renumber.hip, lzf_request.hip, lzf_dispatch.hip), over the byte helpers of
+ * lzf_meta.hip, lzf_reply.hip, lzf_renumber.hip, lzf_request.hip, lzf_dispatch.hip,
+ * lzf_order.hip), over the byte helpers of
  * lzf_dev.h, the geometry of lzf_store_layout.h and the request grammar of
  * lzf_request.h, where the number parse lives.  One copy of each: the pad and the "no
  * entry" class; the ballot count, the 64-bit wave sum and the wave leader's
@@ -142,6 +143,22 @@ __device__ inline uint64_t dv_carry_scan(uint64_t *v, uint32_t n, uint64_t *sw)
 __device__ inline void sd_put32(uint8_t *p, uint32_t x)               /* little-endian, any alignment */
 {
     p[0] = (uint8_t)x; p[1] = (uint8_t)(x >> 8); p[2] = (uint8_t)(x >> 16); p[3] = (uint8_t)(x >> 24);
+}
+
+/* whether the plen bytes at key equal the prefix: whole dwords, the last one
+ * overlapping the one before it when plen is no multiple of 4, so only a
+ * prefix of 1-3 bytes is compared byte by byte.  Most keys leave at the first
+ * dword */
+__device__ inline bool mg_prefix_match(const uint8_t *key, const uint8_t *__restrict__ prefix, uint32_t plen)
+{
+    if (plen < 4u) {
+        bool same = true;
+        for (uint32_t j = 0; j < plen; j++) same &= key[j] == prefix[j];
+        return same;
+    }
+    for (uint32_t j = 0; j + 4u <= plen; j += 4u)
+        if (dv_ld4(key + j) != dv_ld4(prefix + j)) return false;
+    return !(plen & 3u) || dv_ld4(key + plen - 4u) == dv_ld4(prefix + plen - 4u);
 }
 
 /* gbClientEnqueueData's reply header (src/net.c:1162-1205):

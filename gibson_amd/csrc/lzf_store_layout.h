@@ -174,6 +174,41 @@ static inline void lzf_select_layout(LzfSelectArgs &a, LzfCarver &c)
     a.w_tile = c.take<uint64_t>(nt);
 }
 
+/* the node table of the ordered select: a power of two of at least twice the
+ * node words, at least 2; 0 where 2^63 does not hold it */
+static __host__ __device__ inline uint64_t sd_order_slots(uint64_t node_words)
+{
+    if (node_words > (1ull << 62)) return 0ull;
+    uint64_t s = 2ull;
+    while (s < 2ull * node_words) s <<= 1;
+    return s;
+}
+
+/* select_ordered (lzf_order.hip); a table past 2^63 words saturates the size */
+static inline void lzf_order_layout(LzfOrderArgs &a, LzfCarver &c)
+{
+    const uint64_t nt = sd_tiles(a.count), cn = a.cand_cap, ct = sd_tiles(cn);
+    a.slots = sd_order_slots(a.node_cap);
+    c.align(8);
+    a.w_state = c.take<uint64_t>(SD_STATE_WORDS);
+    a.w_mask = c.take<uint64_t>(nt * SD_WORDS);
+    a.w_tile_n = c.take<uint64_t>(nt);
+    a.w_tile_b = c.take<uint64_t>(nt);
+    a.w_tile_m = c.take<uint64_t>(nt);
+    if (!a.slots || a.slots > (~0ull >> 3)) c.pad(~0ull);
+    a.w_table = c.take<uint64_t>(a.slots);
+    a.w_ctile_n = c.take<uint64_t>(ct);
+    a.w_ctile_b = c.take<uint64_t>(ct);
+    a.w_row_off = c.take<uint64_t>(cn);
+    if (a.node_cap > (~0ull >> 2)) c.pad(~0ull);
+    a.w_rows = c.take<uint32_t>(a.node_cap);
+    a.w_cand = c.take<uint32_t>(cn);
+    a.w_live = c.take<uint32_t>(cn);
+    a.w_row_len = c.take<uint32_t>(cn);
+    a.w_sort[0] = c.take<uint32_t>(cn);
+    a.w_sort[1] = c.take<uint32_t>(cn);
+}
+
 /* mget (lzf_mget.hip) */
 static inline void lzf_mget_layout(LzfMgetArgs &a, LzfCarver &c)
 {

@@ -59,6 +59,9 @@ EXPORTS = (
     "lzf_gpu_store_compact",
     "lzf_gpu_store_select_work_size",
     "lzf_gpu_store_select_prefix",
+    "lzf_gpu_store_select_ordered_work_size",
+    "lzf_gpu_store_select_ordered",
+    "lzf_host_store_select_ordered",
     "lzf_gpu_store_mget_work_size",
     "lzf_gpu_store_mget",
     "lzf_gpu_store_count",
@@ -391,6 +394,12 @@ def _bind_store_index(L):
     L.lzf_gpu_store_select_work_size.argtypes = [u32]
     L.lzf_gpu_store_select_prefix.restype = ctypes.c_int
     L.lzf_gpu_store_select_prefix.argtypes = [vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp]
+    L.lzf_gpu_store_select_ordered_work_size.restype = u64
+    L.lzf_gpu_store_select_ordered_work_size.argtypes = [u32, u32, u64, u32]
+    L.lzf_gpu_store_select_ordered.restype = ctypes.c_int
+    L.lzf_gpu_store_select_ordered.argtypes = [vp, vp, vp, vp, u32, vp, u32, i64, u32, u64, vp, u32, vp, vp, vp]
+    L.lzf_host_store_select_ordered.restype = ctypes.c_int
+    L.lzf_host_store_select_ordered.argtypes = [vp, vp, vp, vp, u32, vp, u32, i64, u32, u64, vp, u32, vp]
     L.lzf_gpu_store_mget_work_size.restype = u64
     L.lzf_gpu_store_mget_work_size.argtypes = [u32]
     L.lzf_gpu_store_mget.restype = ctypes.c_int
@@ -892,6 +901,65 @@ def store_select_prefix(keys, key_off, key_len, enc, prefix, sel, result, work=N
                                            _ptr(work), _stream_handle(stream))
     _check(rc, "lzf_gpu_store_select_prefix")
     return work
+
+
+ORDER_OK, ORDER_EWORK = 0, 1                     # lzf_gpu.h: LZF_ORDER_*
+
+
+def store_select_ordered_work(count, cand_cap, node_cap, cap, device):
+    """A scratch tensor for one store_select_ordered call over ``count`` items
+    with room for ``cand_cap`` candidates and ``node_cap`` node words."""
+    import torch
+    size = int(lib().lzf_gpu_store_select_ordered_work_size(int(count), int(cand_cap), int(node_cap), int(cap)))
+    if size == 2**64 - 1:
+        raise ValueError("store_select_ordered_work: the size does not fit 64 bits")
+    return torch.empty(size, dtype=torch.uint8, device=device)
+
+
+def store_select_ordered(keys, key_off, key_len, enc, prefix, sel, result, limit=-1, cand_cap=None, node_cap=None,
+                         work=None, stream=None):
+    """tr_search on the device, in the reference's order: sel (int32, read as
+    u32; its length is the cap) receives the indices of the items that are not
+    ENC_NULL and whose key starts with ``prefix`` (a uint8 tensor on the
+    device) in trie pre-order with the children in creation order, cut to
+    ``limit`` when it is positive, padded with 0xFFFFFFFF (-1).  The order
+    follows from the keys of all the items, dead ones included
+    (include/lzf_gpu.h).  result (5 elements, int64) = entries written, live
+    matches, candidates (matches and dead items of the prefix), node words
+    needed, ORDER_OK or ORDER_EWORK: more candidates than ``cand_cap`` (default:
+    the item count) or more node words than ``node_cap`` (default: the length
+    of ``keys``); sel is then all padding, and result[2] and result[3] say what
+    a repeat needs.  No host wait; returns ``work``
+    (store_select_ordered_work), which must outlive the stream's work."""
+    n = enc.numel()
+    cand_cap = n if cand_cap is None else int(cand_cap)
+    node_cap = max(1, int(keys.numel())) if node_cap is None else int(node_cap)
+    if work is None:
+        work = store_select_ordered_work(n, cand_cap, node_cap, sel.numel(), enc.device)
+    rc = lib().lzf_gpu_store_select_ordered(_ptr(keys), _ptr(key_off), _ptr(key_len), _ptr(enc), n, _ptr(prefix),
+                                            int(prefix.numel()), int(limit), cand_cap, node_cap, _ptr(sel),
+                                            int(sel.numel()), _ptr(result), _ptr(work), _stream_handle(stream))
+    _check(rc, "lzf_gpu_store_select_ordered")
+    return work
+
+
+def host_select_ordered(keys, key_off, key_len, enc, prefix, cap, limit=-1, cand_cap=None, node_cap=None):
+    """lzf_host_store_select_ordered(): the same rule over numpy arrays on the
+    host, as the reference's trie and its walk.  keys/enc/prefix uint8, key_off
+    uint64, key_len uint32.  Returns (sel, result): uint32[cap] and uint64[5]."""
+    import numpy as np
+    k, o = np.ascontiguousarray(keys, np.uint8), np.ascontiguousarray(key_off).astype(np.uint64)
+    ln, e = np.ascontiguousarray(key_len).astype(np.uint32), np.ascontiguousarray(enc, np.uint8)
+    p = np.ascontiguousarray(prefix, np.uint8)
+    if not len(o) == len(ln) == len(e):
+        raise ValueError("host_select_ordered: arrays of different lengths")
+    sel, result = np.zeros(int(cap), np.uint32), np.zeros(5, np.uint64)
+    cand_cap = len(e) if cand_cap is None else int(cand_cap)
+    node_cap = max(1, len(k)) if node_cap is None else int(node_cap)
+    _check(lib().lzf_host_store_select_ordered(_np_ptr(k), _np_ptr(o), _np_ptr(ln), _np_ptr(e), len(e), _np_ptr(p),
+                                               len(p), int(limit), cand_cap, node_cap, _np_ptr(sel), int(cap),
+                                               _np_ptr(result)), "lzf_host_store_select_ordered")
+    return sel, result
 
 
 def store_mget_work(n, device):

@@ -536,13 +536,16 @@ int lzf_gpu_store_remap(uint32_t *idx, uint32_t n, const uint32_t *remap, uint32
  * item_time and item_ttl may both be NULL (nothing expires); exactly one of
  * them NULL is LZF_GPU_EARG.
  *
- * Order is a stated limit.  The select yields matches in ascending item
+ * Order.  lzf_gpu_store_select_prefix yields matches in ascending item
  * index; the reference's tr_search yields them in trie pre-order with the
  * children in creation order (src/trie.c:154-176).  COUNT, MTTL, MDEL and
  * every operator that passes limit = -1 and replies a number do not depend on
  * the order: select -> operator is exact for them.  MGET with a limit, and
  * the reply order of MGET and KEYS, do depend on it: for those the index
- * list must still come from the host's trie.
+ * list comes from lzf_gpu_store_select_ordered, which yields the reference's
+ * order and applies its limit, on the device.  The one limit left: a
+ * renumbering forgets the dead items' keys, and with them which sibling came
+ * first (see there).
  *
  * LZF_GPU_EARG: a NULL pointer (but the optional ones), count == 0, n == 0,
  * and what each call names.  count and n: up to 2^32 - 1; all byte arithmetic
@@ -564,6 +567,74 @@ int lzf_gpu_store_select_prefix(const uint8_t *keys, const uint64_t *key_off, co
                                 const uint8_t *prefix, uint32_t prefix_len,
                                 uint32_t *sel, uint32_t cap, uint32_t *result /* 2 u32 */,
                                 void *work, void *stream);
+
+/*
+ * The ordered prefix select: the live matches in the order of the reference's
+ * tr_search (src/trie.c:154-176), cut to its limit (src/trie.c:162).
+ *
+ * The rule.  The reference never frees a trie node while it runs: tr_remove
+ * clears `data` only and an overwriting tr_insert reuses the node, so a
+ * node's place among its siblings is fixed by the first insert, ever, of a key
+ * with that prefix.  Item indices are handed out in insert order and a dead
+ * item (enc == LZF_ENC_NULL) keeps key_off / key_len and its key bytes until a
+ * renumbering.  So, with birth(P) the smallest index in [0, count) whose key
+ * starts with the byte string P, live or dead, and row(K) of a key K the
+ * sequence birth(K[0..d)) for d = prefix_len + 1 .. len(K): the reference's
+ * order of the live matches is the ascending lexicographic order of their
+ * rows, a row that is a proper prefix of another first -- the key equal to
+ * the prefix first of all, a key before its extensions.
+ *
+ * Candidates are the items i < count with key_len[i] >= prefix_len whose first
+ * prefix_len key bytes equal prefix, whatever enc holds; matches are the live
+ * candidates (enc[i] != LZF_ENC_NULL; an expired item matches, as in the
+ * select above).  limit > 0 keeps the first `limit` matches, limit <= 0 all.
+ * sel[0 .. result[0]) holds them in order, cut to limit and then to cap, and
+ * sel[result[0] .. cap) is 0xFFFFFFFF.  Two live items with the same key --
+ * a store kept by lzf_gpu_key_index_upsert never holds them -- come in
+ * ascending index.
+ *
+ * result (5 device u64): [0] the entries written, [1] the live matches, [2]
+ * the candidates, [3] the node words needed, the sum of key_len - prefix_len
+ * over the candidates, [4] LZF_ORDER_OK or LZF_ORDER_EWORK: the candidates
+ * exceed cand_cap or the node words exceed node_cap.  The call is then
+ * refused whole: all of sel is 0xFFFFFFFF and result[0] = 0, while [1], [2]
+ * and [3] hold what they always hold, so the host repeats the call with
+ * cand_cap >= result[2] and node_cap >= result[3] (the pattern of
+ * LZF_REPLY_TOO_BIG).
+ *
+ * work: lzf_gpu_store_select_ordered_work_size(count, cand_cap, node_cap,
+ * cap) bytes of device scratch that must stay valid until the stream's work is
+ * done; about 12 * count / 64 + 28 * cand_cap bytes and 20 to 36 bytes per
+ * node word (a table of 64-bit words, a power of two of at least twice
+ * node_cap, and the rows).  ~0 when the size does not fit 64 bits; the call is
+ * then LZF_GPU_EARG.  Asynchronous on `stream` with no host wait; every
+ * length the call produces lives in the work area.
+ *
+ * Stated limit.  After lzf_gpu_store_renumber the dead items' keys are gone:
+ * the births are then those of a server into which the surviving items were
+ * inserted in index order.  Keys with a NUL byte stay outside the model, as
+ * for KEYS.
+ *
+ * LZF_GPU_EARG: a NULL pointer, count == 0, prefix_len == 0, cap == 0,
+ * cand_cap == 0, node_cap == 0.
+ *
+ * lzf_host_store_select_ordered is the same rule over host arrays, written as
+ * the trie itself: children in arrival order and a pre-order walk.
+ */
+#define LZF_ORDER_OK    0
+#define LZF_ORDER_EWORK 1
+uint64_t lzf_gpu_store_select_ordered_work_size(uint32_t count, uint32_t cand_cap, uint64_t node_cap, uint32_t cap);
+int lzf_gpu_store_select_ordered(const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                                 const uint8_t *enc, uint32_t count,
+                                 const uint8_t *prefix, uint32_t prefix_len, int64_t limit,
+                                 uint32_t cand_cap, uint64_t node_cap,
+                                 uint32_t *sel, uint32_t cap, uint64_t *result /* 5 u64 */,
+                                 void *work, void *stream);
+int lzf_host_store_select_ordered(const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                                  const uint8_t *enc, uint32_t count,
+                                  const uint8_t *prefix, uint32_t prefix_len, int64_t limit,
+                                  uint32_t cand_cap, uint64_t node_cap,
+                                  uint32_t *sel, uint32_t cap, uint64_t *result /* 5 u64 */);
 
 /*
  * MGET over an index list: what gbQueryMultiGetHandler does after tr_search
@@ -911,7 +982,7 @@ int lzf_gpu_store_meta(const uint32_t *idx, uint32_t n, int field, uint8_t *enc,
  *
  * Keys containing a NUL byte are outside the model: the reference truncates
  * them through strlen (:1367), this call writes all key_len bytes.  Reply
- * order is list order, not the reference's trie order.  work:
+ * order is list order (lzf_gpu_store_select_ordered gives the reference's).  work:
  * lzf_gpu_store_keys_work_size(n) bytes of device scratch that must stay valid
  * until the stream's work is done.  LZF_GPU_EARG: a NULL pointer, n == 0,
  * count == 0.
@@ -959,9 +1030,9 @@ int lzf_gpu_store_keys(const uint32_t *idx, uint32_t n,
  *
  * Locks: SET on a locked item replies REPL_ERR_LOCKED (src/query.c:446-451);
  * lzf_gpu_store_set_guard, run between the lookup of a batch's own keys and
- * its insert, decides that on the device.  Not modelled: the ordered prefix
- * walk, which stays with the host's trie, and the SET reply, which the host
- * builds from the request's bytes it holds.
+ * its insert, decides that on the device.  Not modelled: the SET reply, which
+ * the host builds from the request's bytes it holds.  (The ordered prefix walk
+ * is lzf_gpu_store_select_ordered.)
  */
 #define LZF_KIDX_OK    0
 #define LZF_KIDX_FULL  1   /* *used + n > slots - slots / 4: the batch was refused as a whole */
@@ -1368,7 +1439,8 @@ int lzf_gpu_store_append_keys(const uint8_t *req, uint64_t req_bytes,
  * Inputs: op, status, slot (request order, n entries) and class_first (device);
  * class_mode and class_base, two HOST arrays of LZF_RQ_NCLASS entries that
  * travel in the kernel's arguments -- class_mode[c] is LZF_STITCH_HOST (the
- * host builds the class's replies: PING, STATS, END, the ordered prefix walk),
+ * host builds the class's replies: PING, STATS, END, and MGET / KEYS, whose
+ * frames the host has from lzf_gpu_store_select_ordered and the operator),
  * LZF_STITCH_ARENA (lzf_gpu_store_replies wrote them) or LZF_STITCH_CODE (the
  * class left an entry status), class_base[c] is where class c's reply arena
  * starts inside `replies`; and in bucket order, n entries each, b_rep_off /
@@ -1428,7 +1500,8 @@ int lzf_gpu_store_append_keys(const uint8_t *req, uint64_t req_bytes,
  * observe -- so a client's next request waits for the next batch.  Limits:
  * the index-list operators leave duplicates unspecified, so two DELs or INCs
  * of one key in one batch are the host's to split; the prefix operators'
- * reply order (MGET with a limit, KEYS) still needs the host's trie.
+ * reply order (MGET with a limit, KEYS) comes from
+ * lzf_gpu_store_select_ordered, which the host queues in front of them.
  */
 #define LZF_RQ_NCLASS      23
 
